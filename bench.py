@@ -10,11 +10,18 @@ One timed "step" = one Parareal fine sweep: every slice propagated by the batche
 states.  Weak scaling: every rank owns 128 slices, so the job integrates 128*N slices per step.
 value = (slices x fine steps per slice, all ranks) / max-over-ranks wall time of the K steps.
 
-Also reported (rank 0): nnGP corrections/s (the sequential correction sweep of one iteration on
-the same config), wall-clock to convergence with its K for the full nnGParareal solve of the
-Hopf config and of the Burgers d=128 N=128 config (BASELINE configs[2], the north star's 10x
-target), the FP64-VALU roofline of the fine kernel (HIP events around the launches), and the CPU
-baseline: the oracle's C restatement (OpenMP over slices) on a bounded sample of the same sweep.
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only that: it sets up, warms up, times
+the K steps and prints the JSON result line, with the FP64-VALU roofline of the fine kernel from
+the HIP events around the timed launches.  `--dump-outputs DIR` also writes what the last timed
+step computed, the fine end states a caller of the sweep receives, as DIR/fine_end_states.npy
+(float64); the inputs are seeded, so two builds can be compared output for output.
+
+`--full` adds every other measurement (rank 0): the FHN-PDE strong-scaling workload, nnGP
+corrections/s (the sequential correction sweep of one iteration on the same config), wall-clock to
+convergence with its K for the full nnGParareal solve of the Hopf config and of the Burgers d=128
+N=128 config (BASELINE configs[2], the north star's 10x target), the published runs and K table,
+the correction and GParareal rooflines, and the CPU baseline: the oracle's C restatement (OpenMP
+over slices) on a bounded sample of the same sweep.
 """
 import argparse
 import json
@@ -95,6 +102,27 @@ def barrier_sync(torch, world):
     torch.cuda.synchronize()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each device array as path/<name>.npy (float64, what the timed path
+    handed back), at most DUMP_LIMIT_BYTES in all; a larger array is cut to a fixed, seeded sample
+    of its rows (sorted indices, the same from run to run).  Returns {name: shape written}."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    shapes = {}
+    for name, a in arrays.items():
+        h = np.ascontiguousarray(a.detach().cpu().numpy(), dtype=np.float64)
+        if h.nbytes > budget:
+            h = h.reshape(len(h), -1)
+            keep = max(1, budget // (h.shape[1] * 8))
+            h = h[np.sort(np.random.default_rng(0).choice(len(h), keep, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), h)
+        shapes[name] = list(h.shape)
+    return shapes
+
+
 def hopf_setup(g, steps_per_slice, n_slices):
     ode = g.Hopf(normalization='-11')
     solver = g.SolverRK(ode.get_vector_field(), Ng=2048 // 128, Nf=steps_per_slice, F='RK4', G='RK1',
@@ -102,8 +130,10 @@ def hopf_setup(g, steps_per_slice, n_slices):
     return ode, solver
 
 
-def fine_sweep_bench(torch, g, world, rank, steps, warmup, steps_per_slice, slices_per_rank):
-    """Time K fine sweeps of 128*world slices (weak scaling), HIP events around the kernel."""
+def fine_sweep_bench(torch, g, world, rank, steps, warmup, steps_per_slice, slices_per_rank, check_native=True):
+    """Time K fine sweeps of 128*world slices (weak scaling), HIP events around the kernel.  Returns
+    the end states of the last sweep as its caller receives them: this rank's on one GPU, the
+    all-gathered states of every rank otherwise."""
     n_total = slices_per_rank * world
     ode, solver = hopf_setup(g, steps_per_slice, n_total)
     rng = np.random.default_rng(1234)
@@ -146,7 +176,9 @@ def fine_sweep_bench(torch, g, world, rank, steps, warmup, steps_per_slice, slic
         elapsed = float(tt.item())
     kernel_s = np.mean([a.elapsed_time(b) / 1e3 for a, b in ev])
     check = None
-    if world > 1 and not g.parareal.native_comm_default():
+    if not check_native:
+        pass
+    elif world > 1 and not g.parareal.native_comm_default():
         check = {'nngp_allgather_states_bitwise_torch': None,
                  'note': 'library communicator not exercised: opt-in, NNGP_NATIVE_COMM=1'}
     elif world > 1:   # the library's RCCL all-gather on the same end states, bitwise torch's
@@ -162,7 +194,8 @@ def fine_sweep_bench(torch, g, world, rank, steps, warmup, steps_per_slice, slic
                 check = {'nngp_allgather_states_bitwise_torch': None, 'note': 'library communicator unavailable'}
         except Exception as e:   # a report, never fatal to the headline
             check = {'nngp_allgather_states_bitwise_torch': None, 'error': str(e)[:200]}
-    return elapsed, kernel_s, n_total, out, ('torch all_gather_into_tensor' if world > 1 else None), check
+    return (elapsed, kernel_s, n_total, gathered if world > 1 else out,
+            'torch all_gather_into_tensor' if world > 1 else None, check)
 
 
 def corrections_bench(torch, g, m=15, R=2, n_slices=128):
@@ -810,7 +843,7 @@ def fhn_pde_fine_sweeps(torch, g):
     return res
 
 
-def fhn_strong(torch, g, world, rank, steps=3, warmup=1, sample=400, n_pred=4):
+def fhn_strong(torch, g, world, rank, steps=3, warmup=1, sample=400, n_pred=4, keep_out=False):
     """The north star's strong-scaling workload, FHN-PDE d=800 (d_x=20), N=512 slices, at every
     world size: the fine sweep of all 512 slices sharded into contiguous blocks (512/world per
     rank, fine_sweep_sharded) + the all-gather of the end states, and the nnGP correction of one
@@ -861,6 +894,7 @@ def fhn_strong(torch, g, world, rank, steps=3, warmup=1, sample=400, n_pred=4):
     for _ in range(warmup):
         sweep()
     f_s = timed(sweep, steps)
+    sweep_out = UF[1:].clone() if keep_out else None   # the end states of the last timed sweep
     # nnGP correction of one slice, coordinate-sharded over the ranks (same data on every rank)
     rows, m = 3000, 20
     X = np.clip(np.cumsum(0.01 * rng.standard_normal((rows, d)), axis=0), -1, 1)
@@ -897,6 +931,8 @@ def fhn_strong(torch, g, world, rank, steps=3, warmup=1, sample=400, n_pred=4):
            'iteration_s_projected': f_s / sample * steps_it + (n_sl - 1) * c_s,
            'sample': f'{sample} RK8 steps x 512 slices; {n_pred} corrections of 7200 fits (rows {rows})',
            'correction_sweep': sweep_res}
+    if keep_out:
+        res['_sweep_out'] = sweep_out
     if world == 1:   # the 8-GPU per-rank shares, measured on this GPU
         sh = 64
         sweep8 = lambda: solver.run_F_batch(td[:sh], td[1:sh + 1], Ud[:sh].contiguous(), out=UF[1:sh + 1])
@@ -1034,7 +1070,13 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--steps-per-slice', type=int, default=2048 * 85 * 10000 // 128)   # 13.6e6
     ap.add_argument('--slices-per-gpu', type=int, default=128)
-    ap.add_argument('--no-extras', action='store_true', help='skip corrections/convergence/CPU legs')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, run every other measurement: the FHN-PDE strong-scaling '
+                         'workload, corrections, solves to convergence, published runs, rooflines, CPU legs')
+    ap.add_argument('--no-extras', action='store_true',
+                    help='with --full: only the FHN-PDE strong-scaling workload, no corrections/convergence/CPU legs')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the end states the last timed step computed to DIR/fine_end_states.npy (float64)')
     ap.add_argument('--workload', choices=['hopf', 'fhn_pde'], default='hopf',
                     help="headline value: 'hopf' = BASELINE configs[1] Hopf fine sweep, weak scaling "
                          "(128 slices per GPU); 'fhn_pde' = FHN-PDE d=800 N=512 fine sweep, strong "
@@ -1045,6 +1087,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit('bench.py: --gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit('bench.py: --steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
 
@@ -1070,8 +1114,9 @@ def main():
     import nngp_amd as g
     g.lib()
 
-    elapsed, kernel_s, n_total, _, gather_path, native_check = fine_sweep_bench(
-        torch, g, world, rank, args.steps, args.warmup, args.steps_per_slice, args.slices_per_gpu)
+    elapsed, kernel_s, n_total, end_states, gather_path, native_check = fine_sweep_bench(
+        torch, g, world, rank, args.steps, args.warmup, args.steps_per_slice, args.slices_per_gpu,
+        check_native=args.full)
     total_steps = n_total * args.steps_per_slice * args.steps
     value = total_steps / elapsed
     flops_launch = FLOPS_PER_STEP[('hopf', 'RK4')] * args.steps_per_slice * args.slices_per_gpu
@@ -1099,15 +1144,24 @@ def main():
                                          / (kernel_s / args.steps_per_slice),
                      'flops_per_step_per_slice': FLOPS_PER_STEP[('hopf', 'RK4')]},
     }
-    # the strong-scaling workload (FHN-PDE N=512), measured at every world size
-    strong = fhn_strong(torch, g, world, rank)
-    res['fhn_pde_strong'] = strong
-    if args.workload == 'fhn_pde':
-        res.update({'value': strong['F_steps_per_s'], 'scaling': 'strong',
-                    'ms_per_step': strong['F_us_per_step'] * 400 / 1e3,
-                    'config': {'workload': strong['workload'], 'total_slices': 512, 'd': 800,
-                               'slices_per_gpu': strong['slices_per_rank'], 'parallelism': f'time-slices x{world}'}})
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full or args.workload == 'fhn_pde':
+        # the strong-scaling workload (FHN-PDE N=512), measured at every world size; as the headline
+        # (--workload fhn_pde) its timed sweeps are the --steps / --warmup of the command line
+        headline = args.workload == 'fhn_pde'
+        strong = fhn_strong(torch, g, world, rank, **(dict(steps=args.steps, warmup=args.warmup, keep_out=True)
+                                                      if headline else {}))
+        sweep_out = strong.pop('_sweep_out', None)
+        res['fhn_pde_strong'] = strong
+        if headline:
+            end_states = sweep_out
+            res.update({'value': strong['F_steps_per_s'], 'scaling': 'strong',
+                        'ms_per_step': strong['F_us_per_step'] * 400 / 1e3,
+                        'config': {'workload': strong['workload'], 'total_slices': 512, 'd': 800,
+                                   'slices_per_gpu': strong['slices_per_rank'],
+                                   'parallelism': f'time-slices x{world}'}})
+    if args.dump_outputs and rank == 0:
+        res['outputs'] = dump_outputs(args.dump_outputs, {'fine_end_states': end_states})
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         n_pred, pred_s, _ = corrections_bench(torch, g)
         res['nngp_corrections_per_s'] = n_pred / pred_s
         res['nngp_correction_ms'] = pred_s / n_pred * 1e3

@@ -209,6 +209,24 @@ def test_bench_roofline_traffic_is_the_committed_pmc_figure():
     assert len(tr['traffic_all_launches']) == len(fetch)
 
 
+def test_bench_dump_outputs_writes_float64_within_its_size_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array lands as <name>.npy in float64, bit for bit; an array
+    over the size limit is cut to the same sorted sample of its rows on every run."""
+    import torch
+    import bench
+    a = torch.arange(40 * 3, dtype=torch.float64).reshape(40, 3) / 7
+    assert bench.dump_outputs(str(tmp_path / 'whole'), {'a': a}) == {'a': [40, 3]}
+    w = np.load(tmp_path / 'whole' / 'a.npy')
+    assert w.dtype == np.float64 and np.array_equal(w, a.numpy())
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 10 * 3 * 8)
+    for d in ('s1', 's2'):
+        assert bench.dump_outputs(str(tmp_path / d), {'a': a}) == {'a': [10, 3]}
+    s1, s2 = np.load(tmp_path / 's1' / 'a.npy'), np.load(tmp_path / 's2' / 'a.npy')
+    assert np.array_equal(s1, s2) and s1.nbytes <= 10 * 3 * 8
+    rows = [int(round(r[0] * 7)) // 3 for r in s1]
+    assert rows == sorted(set(rows)) and np.array_equal(s1, a.numpy()[rows])
+
+
 def test_adaptive_nn_warns_up_front_when_n_could_outgrow_the_fits(monkeypatch):
     """nn='adaptive' (m = k+2) past 63 iterations exceeds the GPU fits' m <= 64: Parareal.run says
     so before any work (the run itself raises only if it gets there)."""
