@@ -71,6 +71,10 @@ __global__ void __launch_bounds__(64) rk_lane_kernel(LaneArgs args, int n_slices
 // box (tools/lane_group_probe.py): Hopf RK4 119 -> 97 VALU, 0.250 -> 0.201
 // us/step; Lorenz 0.29 -> 0.19; Thomas labyrinth one sin per lane instead of three, 1.45 -> 0.47;
 // double pendulum one sincos per bank instead of three, 1.82 -> 0.91.
+// Hopf since then (GroupSys<HOPF> below): registers carried across stages (85
+// VALU), one fused `v_fmac_f64_dpp` per RHS and RK4's third stage re-using the second's u2/mu
+// (78), and two steps per loop iteration (the taken branch of a one-step loop is paid in full
+// with one wave per SIMD): 0.1725 -> 0.158 us/step (profiles/r07/bench_before_after.txt).
 // Bitwise the lane kernel: each component is rounded by the same expression in the same order.
 // ---------------------------------------------------------------------------------------------
 template <int CTRL>
@@ -114,15 +118,36 @@ template <> struct GroupSys<NNGP_SYS_HOPF> {     // systems.py:148-154, as LaneS
     static constexpr int G = 16;
     // g = (u2/mu - u0*u0) - u1*u1; component 0: -u1 + u0*g, component 1: u0 + u1*g, component 2: 1.
     // Fewer ops than broadcasting u0, u1, u2 and squaring the broadcasts: every lane squares its
-    // own component (sq = x*x, the same rounded products), and bank-masked `take`s into registers
-    // carried from stage to stage move only what banks 0 and 1 need -- u2 (for u2/mu), u0^2, u1^2
-    // and the coupling term P (bank 0: u1, bank 1: u0) -- while bank 2's lanes keep what `init`
-    // put there: 0 in C, A2, B2, so g = +-0 and x*g = +-0 (u2 is always finite), and 1.0 in P.
+    // own component (sq = x*x, the same rounded products) and divides its own component by mu
+    // (q = x/mu, div_const; only bank 2's is used), and bank-masked DPP ops into registers carried
+    // from stage to stage move only what banks 0 and 1 need -- u2/mu into Q, u1^2 into B2 and the
+    // coupling term P (bank 0: u1, bank 1: u0) -- while bank 2's lanes keep what `init` put there:
+    // 0 in Q, A2, B2, so g = +-0 and x*g = +-0 (u2 is always finite), and 1.0 in P.
     // The sum p + x*g is one fma(S, P, x*g) with S = -1 in bank 0 and +1 elsewhere: S*P is exact,
     // so the fma is the correctly rounded x*g -+ P, bitwise the reference's addition (signed zeros
     // included: the fma's exact-sum rule is the addition's); bank 2: +-0 + 1 = 1.
-    // 13 VALU per RHS instead of 16.  (The contracted build keeps the broadcast form, whose
-    // p + x*g contracts to one fma there.)
+    // By the same argument q - u0^2 is ONE `v_fmac_f64_dpp row_newbcast:0`: Q <- fma(bcast(sq), M,
+    // Q) with M = -1.0 (in a VGPR: the DPP form takes no inline constant) is the correctly rounded
+    // subtraction, in place of a broadcast move plus an add.  12 VALU per RHS.
+    //
+    // Why only one of the four additions is fused, and why this is inline asm: LLVM does not form
+    // v_fmac_f64_dpp, and a DPP op needs EVERY VGPR it reads -- the DPP source, but also the
+    // accumulator and the old value of a bank-masked move -- written at least two wait states
+    // earlier (tools/ubench_dpp_fma.hip: a fused op right behind the op that wrote its
+    // accumulator returns wrong values).  A wait state spent in s_nop costs
+    // more than the move it saves, so a fused op pays only where two useful instructions fit
+    // between it and its accumulator's writer: here the moves of B2 and P.  Each RHS is ONE asm
+    // statement whose order meets every wait state by construction, whatever precedes it: the
+    // first DPP op comes after four plain ops (x is read through DPP no sooner), and between any
+    // write and a DPP read of the same register stand two instructions (or one and `s_nop 0`).
+    //
+    // `repeat`: this stage's u2 input is bitwise the previous stage's (bank 2's f is the constant 1,
+    // so every k_s[2] is the same h*sc2, and the tableau adds the same multiple of it:
+    // group_stage_repeats below), hence so is q = u2/mu: the division and its move are skipped
+    // and Q is used again.  The stage before (`keep`) must then leave Q intact, so it subtracts
+    // u0^2 with a move into A2 and an add (13 VALU); the repeating stage has 8 (+ s_nop 0: nothing
+    // else is left to put between x*x and the first DPP read of x).  RK4: 12 + 13 + 8 + 12.
+    // (The contracted build keeps the broadcast form, whose p + x*g contracts to one fma there.)
 #ifdef NNGP_RK_FMA
     __device__ static double f(double x, int c, double one, const LaneArgs &a) {
         const double A = bcast<0>(x), B = bcast<1>(x), C = bcast<2>(x);
@@ -132,18 +157,59 @@ template <> struct GroupSys<NNGP_SYS_HOPF> {     // systems.py:148-154, as LaneS
     }
 #else
     struct St {
-        double C, A2, B2, P, S;
+        double Q, A2, B2, P, S, M;
     };
-    __device__ static St init(int c) { return St{0.0, 0.0, 0.0, c == 2 ? 1.0 : 0.0, c == 0 ? -1.0 : 1.0}; }
-    __device__ static double f(double x, St &s, double, const LaneArgs &a) {
-        const double sq = x * x;
-        s.C = take<8, 0x3>(s.C, x);
-        s.A2 = take<0, 0x3>(s.A2, sq);
-        s.B2 = take<4, 0x3>(s.B2, sq);
-        s.P = take<0, 0x2>(take<4, 0x1>(s.P, x), x);
-        const double g = (div_const(s.C, a.param[0], a.rparam0) - s.A2) - s.B2;
-        return __builtin_fma(s.S, s.P, x * g);
+    __device__ static St init(int c) {
+        return St{0.0, 0.0, 0.0, c == 2 ? 1.0 : 0.0, c == 0 ? -1.0 : 1.0, -1.0};
     }
+    // q = x/mu (div_const) and sq = x*x in every lane, then P, Q, B2 in an order that leaves two
+    // instructions between each register's write and its DPP read: q -> (sq, P) -> Q;
+    // sq -> (P, Q) -> B2; P -> (Q, B2) -> P; Q -> (B2, P) -> the op after this block
+#define NNGP_HOPF_HEAD                                                        \
+    "v_mul_f64 %[q], %[x], %[r]\n\t"                                          \
+    "v_fma_f64 %[e], -%[q], %[b], %[x]\n\t"                                   \
+    "v_fma_f64 %[q], %[e], %[r], %[q]\n\t"                                    \
+    "v_mul_f64 %[sq], %[x], %[x]\n\t"                                         \
+    "v_mov_b64_dpp %[P], %[x] row_newbcast:4 row_mask:0xf bank_mask:0x1\n\t"   \
+    "v_mov_b64_dpp %[Q], %[q] row_newbcast:8 row_mask:0xf bank_mask:0x3\n\t"   \
+    "v_mov_b64_dpp %[B2], %[sq] row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t" \
+    "v_mov_b64_dpp %[P], %[x] row_newbcast:0 row_mask:0xf bank_mask:0x2\n\t"
+    // g = (q - u0^2) - u1^2 from FROM = q - u0^2, then x*g and fma(S, P, x*g)
+#define NNGP_HOPF_TAIL(FROM)                        \
+    "v_add_f64 %[t], %[" FROM "], -%[B2]\n\t"       \
+    "v_mul_f64 %[t], %[x], %[t]\n\t"                \
+    "v_fma_f64 %[o], %[S], %[P], %[t]"
+    __device__ static double f(double x, St &s, bool repeat, bool keep, const LaneArgs &a) {
+        double o, sq, e, q, t;
+        if (repeat) {   // Q is the previous stage's and is used up here: P -> (B2, fused) -> P
+            asm("v_mul_f64 %[sq], %[x], %[x]\n\t"
+                "s_nop 0\n\t"
+                "v_mov_b64_dpp %[P], %[x] row_newbcast:4 row_mask:0xf bank_mask:0x1\n\t"
+                "v_mov_b64_dpp %[B2], %[sq] row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"
+                "v_fmac_f64_dpp %[Q], %[sq], %[M] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"
+                "v_mov_b64_dpp %[P], %[x] row_newbcast:0 row_mask:0xf bank_mask:0x2\n\t"
+                NNGP_HOPF_TAIL("Q")
+                : [o] "=&v"(o), [sq] "=&v"(sq), [t] "=&v"(t), [Q] "+v"(s.Q), [B2] "+v"(s.B2), [P] "+v"(s.P)
+                : [x] "v"(x), [S] "v"(s.S), [M] "v"(s.M));
+        } else if (keep) {   // Q stays q for the next stage
+            asm(NNGP_HOPF_HEAD
+                "v_mov_b64_dpp %[A2], %[sq] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"
+                "v_add_f64 %[t], %[Q], -%[A2]\n\t" NNGP_HOPF_TAIL("t")
+                : [o] "=&v"(o), [sq] "=&v"(sq), [t] "=&v"(t), [e] "=&v"(e), [q] "=&v"(q), [Q] "+v"(s.Q),
+                  [A2] "+v"(s.A2), [B2] "+v"(s.B2), [P] "+v"(s.P)
+                : [x] "v"(x), [S] "v"(s.S), [b] "v"(a.param[0]), [r] "v"(a.rparam0));
+        } else {
+            asm(NNGP_HOPF_HEAD
+                "v_fmac_f64_dpp %[Q], %[sq], %[M] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"
+                NNGP_HOPF_TAIL("Q")
+                : [o] "=&v"(o), [sq] "=&v"(sq), [t] "=&v"(t), [e] "=&v"(e), [q] "=&v"(q), [Q] "+v"(s.Q),
+                  [B2] "+v"(s.B2), [P] "+v"(s.P)
+                : [x] "v"(x), [S] "v"(s.S), [M] "v"(s.M), [b] "v"(a.param[0]), [r] "v"(a.rparam0));
+        }
+        return o;
+    }
+#undef NNGP_HOPF_HEAD
+#undef NNGP_HOPF_TAIL
 #endif
 };
 template <> struct GroupSys<NNGP_SYS_THOMAS_LABYRINTH> {   // systems.py:257-271
@@ -209,6 +275,42 @@ template <class GS> struct GroupState<GS, std::void_t<typename GS::St>> {
     __device__ static T init(int c) { return GS::init(c); }
 };
 
+// Stage s adds to u exactly what stage s-1 added, taken one stage later: rows s and s-1 of the
+// tableau each have a single non-zero entry, of the same value, on k_{s-1} and k_{s-2}.  A
+// component whose f is the same constant at every stage (all its k_j bitwise equal) then has the
+// same stage input at s as at s-1, and a group RHS may carry what it derived from it (RK4: s = 2,
+// u + k0/2 and u + k1/2; no stage of RK1, RK2 or RK8).
+template <typename T>
+__host__ __device__ constexpr bool group_stage_repeats(int s) {
+    if (s < 2 || s >= T::S) return false;
+    for (int j = 0; j < s; j++) {
+        if ((T::A[s][j] != 0.0) != (j == s - 1)) return false;
+        if (j < s - 1 && (T::A[s - 1][j] != 0.0) != (j == s - 2)) return false;
+    }
+    return T::A[s][s - 1] == T::A[s - 1][s - 2];
+}
+template <typename T>
+constexpr int group_repeat_count() {   // -1: two repeating stages in a row
+    int n = 0;
+    for (int s = 0; s <= T::S; s++) {
+        if (group_stage_repeats<T>(s) && group_stage_repeats<T>(s + 1)) return -1;
+        n += group_stage_repeats<T>(s);
+    }
+    return n;
+}
+static_assert(group_stage_repeats<Tableau<4>>(2) && group_repeat_count<Tableau<4>>() == 1,
+              "RK4: the third stage, and only it, repeats");
+static_assert(group_repeat_count<Tableau<1>>() == 0 && group_repeat_count<Tableau<2>>() == 0 &&
+              group_repeat_count<Tableau<8>>() == 0, "RK1, RK2, RK8: no stage repeats");
+
+// stage s of the group RHS: a field with carried state (St) is told whether the stage repeats and
+// whether the next one will (never both: what a stage keeps, the next uses up)
+template <int SYS, typename T, typename G>
+__device__ __forceinline__ double group_f(int s, double x, G &gst, double one, const LaneArgs &args) {
+    if constexpr (std::is_same_v<G, int>) return GroupSys<SYS>::f(x, gst, one, args);
+    else return GroupSys<SYS>::f(x, gst, group_stage_repeats<T>(s), group_stage_repeats<T>(s + 1), args);
+}
+
 template <int SYS> struct has_group { static constexpr bool value = false; };
 template <> struct has_group<NNGP_SYS_LORENZ> { static constexpr bool value = true; };
 template <> struct has_group<NNGP_SYS_HOPF> { static constexpr bool value = true; };
@@ -251,18 +353,26 @@ __global__ void __launch_bounds__(64) rk_group_kernel(LaneArgs args, int n_slice
     const int64_t j0 = j0s ? j0s[i] : 0;
     LinGrid grid;
     if constexpr (LINSPACE) grid.init(j0, gsteps, T0, dt);
-    for (int64_t n = 0; n < steps; n++) {
+    auto step = [&](int64_t n) __attribute__((always_inline)) {
         const double h = LINSPACE ? grid.next(n, T0, T1, dt) : dt;
 #pragma unroll
         for (int s = 0; s < S; s++) {
             const double tmp = stage_input<T, 1>(s, u, k, 0);
             double o;
-            if constexpr (NORM) o = GroupSys<SYS>::f((tmp + 1) * hw + mn, gst, one, args) * sc;
-            else o = GroupSys<SYS>::f(tmp, gst, one, args);
+            if constexpr (NORM) o = group_f<SYS, T>(s, (tmp + 1) * hw + mn, gst, one, args) * sc;
+            else o = group_f<SYS, T>(s, tmp, gst, one, args);
             k[s] = h * o;
         }
         u = step_update<T, 1>(u, k, 0);
+    };
+    // two steps per iteration and a remainder step: the step is one wave's instruction issue with no
+    // other wave on the SIMD to cover the loop's taken branch
+    int64_t n = 0;
+    for (; n + 1 < steps; n += 2) {
+        step(n);
+        step(n + 1);
     }
+    if (n < steps) step(n);
     if (writer) uF[(size_t)i * D + c] = u;
 }
 
