@@ -54,7 +54,9 @@ enum nngp_system_kind {
     NNGP_SYS_BRUSSELATOR = 5,       /* systems.py:202-222                                  */
     NNGP_SYS_DBL_PEND = 6,          /* systems.py:175-199                                  */
     NNGP_SYS_BURGERS = 7,           /* systems.py:402-459, nx = d, param[0] = nu           */
-    NNGP_SYS_FHN_PDE = 8            /* systems.py:291-398, nx = d_x, d = 2*d_x*d_x         */
+    NNGP_SYS_FHN_PDE = 8,           /* systems.py:291-398, nx = d_x, d = 2*d_x*d_x         */
+    NNGP_SYS_DIFFREACT = 9          /* systems.py:463-577, nx = d_x (3..32), d = 2*nx*nx, state u | v,
+                                       param[0..2] = Du, Dv, k; zero-flux walls             */
 };
 
 /* Explicit Runge-Kutta tableaux, RK.py:30-48 (value = order). */
@@ -78,9 +80,10 @@ enum nngp_step_mode { NNGP_STEP_FIXED = 0, NNGP_STEP_LINSPACE = 1, NNGP_STEP_CON
 typedef struct nngp_system {
     int32_t kind;        /* enum nngp_system_kind                                         */
     int32_t d;           /* state dimension                                               */
-    int32_t nx;          /* grid points per axis (Burgers: d; FHN_PDE: d_x); else 0        */
+    int32_t nx;          /* grid points per axis (Burgers: d; FHN_PDE, DIFFREACT: d_x); else 0 */
     int32_t normalized;  /* 0: identity, 1: '-11' wrapper                                 */
-    double param[4];     /* HOPF: [0]=maxtime (tspan[1]); BURGERS: [0]=nu; else unused     */
+    double param[4];     /* HOPF: [0]=maxtime (tspan[1]); BURGERS: [0]=nu; DIFFREACT: [0..2]=Du, Dv, k;
+                            else unused                                                   */
     const double *norm;  /* DEVICE [3*d] = mn | (mx-mn) | 2/(mx-mn), or NULL if identity   */
 } nngp_system;
 

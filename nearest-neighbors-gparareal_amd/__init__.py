@@ -7,11 +7,11 @@ from .configs import Config
 from .models import BareParareal, GPjax_p, ModelAbstr, NNGP_p
 from .parareal import GpuPool, MyPool, Parareal, PararealLight
 from .solver import SolverAbstr, SolverRK
-from .systems import (ODE, Brusselator, Burgers, DblPend, FHN_ODE, FHN_PDE, Hopf, Lorenz, Rossler,
+from .systems import (ODE, Brusselator, Burgers, DblPend, DiffReact, FHN_ODE, FHN_PDE, Hopf, Lorenz, Rossler,
                       ThomasLabyrinth, VectorField)
 from .utils import Normalize
 
 __all__ = ['Config', 'BareParareal', 'ModelAbstr', 'NNGP_p', 'GpuPool', 'MyPool', 'Parareal',
-           'SolverAbstr', 'SolverRK', 'ODE', 'Brusselator', 'Burgers', 'DblPend', 'FHN_ODE',
+           'SolverAbstr', 'SolverRK', 'ODE', 'Brusselator', 'Burgers', 'DblPend', 'DiffReact', 'FHN_ODE',
            'FHN_PDE', 'Hopf', 'Lorenz', 'Rossler', 'ThomasLabyrinth', 'VectorField', 'Normalize',
            'NNGPError', 'build', 'lib']

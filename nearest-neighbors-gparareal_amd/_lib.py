@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, 'csrc')
 
 # enums (include/nngp.h)
 SYS_LORENZ, SYS_HOPF, SYS_THOMAS_LABYRINTH, SYS_FHN_ODE, SYS_ROSSLER = 0, 1, 2, 3, 4
-SYS_BRUSSELATOR, SYS_DBL_PEND, SYS_BURGERS, SYS_FHN_PDE = 5, 6, 7, 8
+SYS_BRUSSELATOR, SYS_DBL_PEND, SYS_BURGERS, SYS_FHN_PDE, SYS_DIFFREACT = 5, 6, 7, 8, 9
 TABLEAU = {'RK1': 1, 'RK2': 2, 'RK4': 4, 'RK8': 8}
 STEP_FIXED, STEP_LINSPACE, STEP_CONTRACT = 0, 1, 16
 

@@ -8,8 +8,9 @@
 //   * lane kernel  (ODEs, d <= 4): one lane = one slice, state + all S stage vectors in VGPRs,
 //     no LDS, no barriers.  The RHS is a handful of dependent fp64 ops, so a slice is a serial
 //     chain of 10^3..10^9 RK steps: this shape is latency-bound by construction.
-//   * field kernel (Burgers d=nx, FHN-PDE d=2 nx^2): one workgroup = one slice, thread t owns
-//     elements t, t+BT, ... (EPT per thread, u and the S stage vectors in VGPRs).  The stage input
+//   * field kernel (Burgers d=nx, FHN-PDE and DiffReact d=2 nx^2): one workgroup = one slice,
+//     thread t owns elements t, t+BT, ... (EPT per thread, u and the S stage vectors in VGPRs;
+//     from 16x16 points the two 2-D fields run one thread per grid point).  The stage input
 //     is staged (already inverse-normalised) in a double-buffered LDS image so the stencil reads
 //     neighbours from LDS; exactly one __syncthreads per stage.
 // HBM traffic is 16*d bytes per slice per launch (read u0, write uF); everything else stays on
@@ -440,6 +441,70 @@ __device__ __forceinline__ double fhn_lap(const double *__restrict__ V, const Nb
     return s;
 }
 
+// DiffReact (systems.py:463-577): zero-flux 5-point Laplacian of grid point p = y*nx + x.  The
+// reference stores it as DIA with offsets [0, -1, 1, -nx, nx] (systems.py:528-530) and scipy's
+// DIA product adds the diagonals in that order, so row p is
+//     main_p w[p] + cx w[p-1] + cx w[p+1] + cy w[p-nx] + cy w[p+nx]
+// summed left to right, a neighbour across a wall giving no term.  Here a wall neighbour is the
+// point itself with coefficient 0.0: adding 0.0*w[p] changes at most the sign of an exact zero
+// (scipy does the same for the in-row wraps, whose stored entries are 0), and every lane runs the
+// same five products.  Chosen once per point, before the step loop: the four neighbour indices,
+// the four "has a neighbour" flags and the main-diagonal entry (one of four values).
+struct DrNbr {
+    int l, r, dn, up;       // p-1, p+1, p-nx, p+nx, or p at a wall
+    bool hl, hr, hd, hu;
+    double main;
+};
+
+__device__ __forceinline__ DrNbr dr_neighbours(const FieldArgs &fa, int p, bool live) {
+    const int nx = fa.nx;
+    const int y = p / nx, x = p - y * nx;
+    DrNbr n;
+    n.hl = live && x > 0;
+    n.hr = live && x < nx - 1;
+    n.hd = live && y > 0;
+    n.hu = live && y < nx - 1;
+    n.l = n.hl ? p - 1 : p;
+    n.r = n.hr ? p + 1 : p;
+    n.dn = n.hd ? p - nx : p;
+    n.up = n.hu ? p + nx : p;
+    const bool ex = !(n.hl && n.hr), ey = !(n.hd && n.hu);   // first/last of its row / column
+    n.main = ex ? (ey ? fa.r_m11 : fa.r_m12) : (ey ? fa.r_m21 : fa.r_m22);
+    return n;
+}
+
+// (lap @ w)_p from the point's own value and its four neighbours', in the DIA order
+__device__ __forceinline__ double dr_lap(double c, double wl, double wr, double wd, double wu, double main,
+                                         double kl, double kr, double kd, double ku) {
+    double s = main * c;
+    s = s + kl * wl;
+    s = s + kr * wr;
+    s = s + kd * wd;
+    s = s + ku * wu;
+    return s;
+}
+
+// systems.py:558-563 (u**3 = u*(u*u)): u_t = (((u - u^3) - k) - v) + Du*lap(u)
+__device__ __forceinline__ double dr_fu(double u, double v, double lap, const FieldArgs &fa) {
+    return (((u - u * (u * u)) - fa.r_k) - v) + fa.r_du * lap;
+}
+// v_t = (u - v) + Dv*lap(v)
+__device__ __forceinline__ double dr_fv(double u, double v, double lap, const FieldArgs &fa) {
+    return (u - v) + fa.r_dv * lap;
+}
+
+// element e of the state u | v from the image V[d] (rk_field_kernel, rhs_field_kernel); nb is the
+// stencil of its grid point (e, or e - d/2 for a v element)
+__device__ __forceinline__ double dr_elem(const double *__restrict__ V, int e, int half, const DrNbr &nb,
+                                          const FieldArgs &fa) {
+    const bool isv = e >= half;
+    const double *W = V + (isv ? half : 0);
+    const int p = isv ? e - half : e;
+    const double lap = dr_lap(W[p], W[nb.l], W[nb.r], W[nb.dn], W[nb.up], nb.main, nb.hl ? fa.r_cx : 0.0,
+                              nb.hr ? fa.r_cx : 0.0, nb.hd ? fa.r_cy : 0.0, nb.hu ? fa.r_cy : 0.0);
+    return isv ? dr_fv(V[p], V[e], lap, fa) : dr_fu(V[e], V[half + e], lap, fa);
+}
+
 // <= 256 threads per slice leaves ~170 VGPRs for u, the S stage vectors and the neighbour table
 template <int SYS, int ORDER, bool LINSPACE, int EPT, bool NORM>
 __global__ void __launch_bounds__(EPT == 1 ? 1024 : (EPT == 2 ? 512 : 256)) rk_field_kernel(FieldArgs fa, int n_slices,
@@ -460,6 +525,7 @@ __global__ void __launch_bounds__(EPT == 1 ? 1024 : (EPT == 2 ? 512 : 256)) rk_f
     double u[EPT], k[S * EPT], mn[EPT], w[EPT], sc[EPT];
     int e_[EPT];
     Nbr5 nb[(SYS == NNGP_SYS_FHN_PDE) ? EPT : 1];
+    DrNbr rnb[(SYS == NNGP_SYS_DIFFREACT) ? EPT : 1];
 #pragma unroll
     for (int r = 0; r < EPT; r++) {
         const int e = tid + r * BT;
@@ -474,6 +540,7 @@ __global__ void __launch_bounds__(EPT == 1 ? 1024 : (EPT == 2 ? 512 : 256)) rk_f
             mn[r] = 0.0; w[r] = 1.0; sc[r] = 1.0;
         }
         if constexpr (SYS == NNGP_SYS_FHN_PDE) nb[r] = fhn_neighbours(fa.nx, ok ? (e % half) : 0);
+        if constexpr (SYS == NNGP_SYS_DIFFREACT) rnb[r] = dr_neighbours(fa, ok ? (e % half) : 0, ok);
     }
     const double T0 = t0[slice], T1 = t1[slice];
     const double dt = (T1 - T0) / (double)(LINSPACE ? gsteps : steps);
@@ -501,6 +568,8 @@ __global__ void __launch_bounds__(EPT == 1 ? 1024 : (EPT == 2 ? 512 : 256)) rk_f
                 if (e < d) {
                     if constexpr (SYS == NNGP_SYS_BURGERS) {
                         f = burgers_elem(V, e, d, fa);
+                    } else if constexpr (SYS == NNGP_SYS_DIFFREACT) {
+                        f = dr_elem(V, e, half, rnb[r], fa);
                     } else {   // FHN_PDE, systems.py:365-366
                         if (e < half) {
                             const double lu = fhn_lap(V, nb[r], fa.a_off, fa.a_diag);
@@ -669,6 +738,106 @@ __global__ void __launch_bounds__(1024) rk_fhn_pair_kernel(FieldArgs fa, int n_s
 }
 
 // ---------------------------------------------------------------------------------------------
+// DiffReact with one thread per grid point, as rk_fhn_pair_kernel: thread p owns u[p] and v[p] with
+// all their stage values, the images are interleaved [point][u, v] with FhnPairImages' stage
+// schedule, and a stage is one 128-bit LDS write, one barrier and FOUR 128-bit reads (the centre
+// comes from registers).  The stencil does not wrap, so there is no column order to sort: the
+// four neighbour slots are p-1, p+1, p-nx, p+nx, and at a wall the thread's own slot with
+// coefficient 0.0 (dr_neighbours) -- both chosen once per thread, so the step loop has no branch.
+// Threads past the grid are "all walls": they read and write only their own slot p < blockDim.x,
+// which lies in the images' padding (the image stride is the block size), never a live point.
+// Same expressions in the same order as dr_elem -- bitwise rk_field_kernel<DIFFREACT>.
+// nx <= 32: at most 1024 points = the launch bound; LDS 16 B * blockDim.x * 3 images <= 48 KiB.
+// ---------------------------------------------------------------------------------------------
+template <int ORDER, bool LINSPACE, bool NORM>
+__global__ void __launch_bounds__(1024) rk_dr_pair_kernel(FieldArgs fa, int n_slices,
+                                                          const double *__restrict__ t0,
+                                                          const double *__restrict__ t1, int64_t steps,
+                                                          int64_t gsteps, const int64_t *__restrict__ j0s,
+                                                          const double *__restrict__ u0,
+                                                          double *__restrict__ uF) {
+    using T = Tableau<ORDER>;
+    using IM = FhnPairImages<T::S>;
+    constexpr int S = T::S;
+    extern __shared__ __attribute__((aligned(16))) double smem[];   // [IM::N][blockDim.x][2]
+    const int slice = blockIdx.x;
+    const int p = threadIdx.x;
+    const int d = fa.d, half = d / 2;
+    const bool ok = p < half;
+    double u[2], k[S * 2], mn[2], w[2], sc[2];
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const int e = p + r * half;
+        u[r] = ok ? u0[(size_t)slice * d + e] : 0.0;
+        if (NORM && ok) {
+            mn[r] = fa.norm[e];
+            w[r] = 0.5 * fa.norm[d + e];   // (mx-mn)/2, see lane_rhs
+            sc[r] = fa.norm[2 * d + e];
+        } else {
+            mn[r] = 0.0; w[r] = 1.0; sc[r] = 1.0;
+        }
+    }
+    const DrNbr nb = dr_neighbours(fa, p, ok);   // the same stencil for u and v
+    const double kl = nb.hl ? fa.r_cx : 0.0, kr = nb.hr ? fa.r_cx : 0.0, kd = nb.hd ? fa.r_cy : 0.0,
+                 ku = nb.hu ? fa.r_cy : 0.0, km = nb.main;
+    const double T0 = t0[slice], T1 = t1[slice];
+    const double dt = (T1 - T0) / (double)(LINSPACE ? gsteps : steps);
+    const int64_t j0 = j0s ? j0s[slice] : 0;
+    LinGrid grid;
+    if constexpr (LINSPACE) grid.init(j0, gsteps, T0, dt);
+    // stage 0's input is u itself (RK.py:153-166: no a_0j terms)
+    double xw[2];
+#pragma unroll
+    for (int r = 0; r < 2; r++) xw[r] = NORM ? (u[r] + 1) * w[r] + mn[r] : u[r];
+    const int ISTR = 2 * (int)blockDim.x;   // doubles per image
+    for (int64_t n = 0; n < steps; n++) {
+        const double h = LINSPACE ? grid.next(n, T0, T1, dt) : dt;
+        double acc[2];   // sum_s b_s k_s, accumulated as the stages finish (step_update's order)
+#pragma unroll
+        for (int s = 0; s < S; s++) {
+            const int img = (S == 1) ? (int)(n & 1) : IM::of(s);
+            double2 *V2 = reinterpret_cast<double2 *>(smem + img * ISTR);
+            V2[p] = make_double2(xw[0], xw[1]);
+            __syncthreads();
+            const double2 wl = V2[nb.l], wr = V2[nb.r], wd = V2[nb.dn], wu = V2[nb.up];
+            // the next stage's input terms that do not involve this stage's k (as rk_fhn_pair_kernel)
+            double pn[2] = {0.0, 0.0};
+            if (s + 1 < S) {
+#pragma unroll
+                for (int r = 0; r < 2; r++) pn[r] = stage_partial<T, 2>(s + 1, k, r);
+            }
+            const double lu = dr_lap(xw[0], wl.x, wr.x, wd.x, wu.x, km, kl, kr, kd, ku);
+            const double lv = dr_lap(xw[1], wl.y, wr.y, wd.y, wu.y, km, kl, kr, kd, ku);
+            double fu = dr_fu(xw[0], xw[1], lu, fa);
+            double fv = dr_fv(xw[0], xw[1], lv, fa);
+            if (NORM) {
+                fu = fu * sc[0];
+                fv = fv * sc[1];
+            }
+            k[s * 2 + 0] = h * fu;
+            k[s * 2 + 1] = h * fv;
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                step_accumulate<T>(s, acc[r], k[s * 2 + r]);   // RK.py:170, in its order
+                if (s + 1 < S) {
+                    const double x = stage_finish<T, 2>(s + 1, u[r], pn[r], k, r);
+                    xw[r] = NORM ? (x + 1) * w[r] + mn[r] : x;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            u[r] = u[r] + acc[r];   // RK.py:170
+            xw[r] = NORM ? (u[r] + 1) * w[r] + mn[r] : u[r];
+        }
+    }
+    if (ok) {
+        uF[(size_t)slice * d + p] = u[0];
+        uF[(size_t)slice * d + half + p] = u[1];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Burgers with d = 64*EPT: ONE WAVE per slice, no LDS, no barriers.
 // Lane l owns the contiguous elements l*EPT .. l*EPT+EPT-1; the periodic stencil's outer
 // neighbours come from lanes l-1 / l+1 by `wave_ror:1` / `wave_rol:1` DPP moves, which wrap around
@@ -732,6 +901,8 @@ __global__ void __launch_bounds__(256) rhs_field_kernel(FieldArgs fa, const doub
         double f;
         if constexpr (SYS == NNGP_SYS_BURGERS) {
             f = burgers_elem(V, e, d, fa);
+        } else if constexpr (SYS == NNGP_SYS_DIFFREACT) {
+            f = dr_elem(V, e, half, dr_neighbours(fa, e < half ? e : e - half, true), fa);
         } else if (e < half) {
             const Nbr5 nb = fhn_neighbours(fa.nx, e);
             const double u1 = V[e];
@@ -850,6 +1021,25 @@ static int field_args(const nngp_system *sys, FieldArgs &fa) {
         fa.c_off = nu / (dx * dx);   // (nu/dx**2)*Txx
         fa.c_diag = fa.c_off * -2.0;
         fa.c_grad = 1 / (2 * dx);    // (1/(2*dx))*Tx
+    } else if (sys->kind == NNGP_SYS_DIFFREACT) {
+        // one workgroup per slice, at most one thread per grid point: 32 x 32 points is the launch
+        // bound (d <= 2048, the FHN-PDE paths' ceiling)
+        NNGP_REQUIRE(sys->nx >= 3 && sys->nx <= 32, "DiffReact needs 3 <= nx <= 32 (got nx=%d): larger grids "
+                     "need a multi-workgroup propagator", sys->nx);
+        NNGP_REQUIRE(sys->d == 2 * sys->nx * sys->nx, "DiffReact needs d = 2 nx^2 (got d=%d, nx=%d)", sys->d,
+                     sys->nx);
+        // systems.py:496-522, in double exactly as the Python expressions (dx**2 = dx*dx)
+        const double dx = (1.0 - (-1.0)) / sys->nx, dy = (1.0 - (-1.0)) / sys->nx;
+        const double dx2 = dx * dx, dy2 = dy * dy;
+        fa.r_cx = 1.0 / dx2;
+        fa.r_cy = 1.0 / dy2;
+        fa.r_m22 = -2.0 / dx2 - 2.0 / dy2;
+        fa.r_m12 = -1.0 / dx2 - 2.0 / dy2;   // first/last point of a row
+        fa.r_m21 = -2.0 / dx2 - 1.0 / dy2;   // first/last row
+        fa.r_m11 = -1.0 / dx2 - 1.0 / dy2;   // corners
+        fa.r_du = sys->param[0];
+        fa.r_dv = sys->param[1];
+        fa.r_k = sys->param[2];
     } else {
         NNGP_REQUIRE(sys->nx >= 3 && sys->d == 2 * sys->nx * sys->nx, "FHN_PDE needs d = 2 nx^2, nx >= 3");
         const double dx = (1.0 - (-1.0)) / (sys->nx - 1);
@@ -910,6 +1100,20 @@ static int launch_field(const nngp_system *sys, int n, const double *t0, const d
             return NNGP_OK;
         }
     }
+    // DiffReact from 16x16 grid points (nx 16..32): one thread per point, as FHN-PDE above; a forced
+    // thread count (NNGP_RK_THREADS) selects the element kernel
+    if (SYS == NNGP_SYS_DIFFREACT && sys->d / 2 >= 256 && sys->d / 2 <= 1024 && !getenv("NNGP_RK_THREADS")) {
+        const int bt = ((sys->d / 2 + 63) / 64) * 64;
+        const size_t lds = sizeof(double) * 2 * bt * FhnPairImages<Tableau<ORDER>::S>::N;
+        if (fa.normalized)
+            hipLaunchKernelGGL((rk_dr_pair_kernel<ORDER, LIN, true>), dim3(n), dim3(bt), lds, st, fa, n, t0, t1,
+                               steps, gsteps, j0, u0, uF);
+        else
+            hipLaunchKernelGGL((rk_dr_pair_kernel<ORDER, LIN, false>), dim3(n), dim3(bt), lds, st, fa, n, t0, t1,
+                               steps, gsteps, j0, u0, uF);
+        NNGP_LAUNCH_CHECK();
+        return NNGP_OK;
+    }
     const int bt = pick_threads(sys->d, n);
     const int ept = (sys->d + bt - 1) / bt;
     NNGP_REQUIRE(ept <= 8, "d=%d with %d threads per slice exceeds the field kernel's 8 elements per thread",
@@ -941,6 +1145,8 @@ static int dispatch_sys(const nngp_system *s, int n, const double *t0, const dou
     case NNGP_SYS_DBL_PEND: return launch_lane<NNGP_SYS_DBL_PEND, ORDER, LIN>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
     case NNGP_SYS_BURGERS: return launch_field<NNGP_SYS_BURGERS, ORDER, LIN>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
     case NNGP_SYS_FHN_PDE: return launch_field<NNGP_SYS_FHN_PDE, ORDER, LIN>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    case NNGP_SYS_DIFFREACT:
+        return launch_field<NNGP_SYS_DIFFREACT, ORDER, LIN>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
     default: set_error("unknown system kind %d", s->kind); return NNGP_E_ARG;
     }
 }
@@ -1017,6 +1223,7 @@ extern "C" int nngp_rhs_batch(const nngp_system *sys, int n, const double *u, do
     case NNGP_SYS_DBL_PEND: return launch_rhs_lane<NNGP_SYS_DBL_PEND>(sys, n, u, out, st);
     case NNGP_SYS_BURGERS: return launch_rhs_field<NNGP_SYS_BURGERS>(sys, n, u, out, st);
     case NNGP_SYS_FHN_PDE: return launch_rhs_field<NNGP_SYS_FHN_PDE>(sys, n, u, out, st);
+    case NNGP_SYS_DIFFREACT: return launch_rhs_field<NNGP_SYS_DIFFREACT>(sys, n, u, out, st);
     default: set_error("unknown system kind %d", sys->kind); return NNGP_E_ARG;
     }
 }

@@ -223,6 +223,9 @@ struct FieldArgs {
     const double *norm;   // device [3d] = mn | w | sc, or nullptr
     double c_off, c_diag, c_grad;   // Burgers: nu/dx^2, -2 nu/dx^2, 1/(2dx)
     double a_off, a_diag, b_off, b_diag;   // FHN-PDE: a*L and b*L entries
+    // DiffReact: 1/dx^2, 1/dy^2, the main diagonal -(a)/dx^2 - (b)/dy^2 with a (b) = 2 inside a
+    // row (column) and 1 at its two ends (m_ab), and Du, Dv, k
+    double r_cx, r_cy, r_m22, r_m12, r_m21, r_m11, r_du, r_dv, r_k;
 };
 
 __device__ __forceinline__ double wave_prev(double v) {   // lane i <- lane i-1 (lane 0 <- 63)

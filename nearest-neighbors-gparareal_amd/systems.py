@@ -6,7 +6,7 @@ RHS on the GPU through nngp_rhs_batch.
 
 Reference: /root/reference/systems.py (ODE 23-77, FHN_ODE 80-106, Rossler 109-137, Hopf 140-172,
 DblPend 175-199, Brusselator 202-222, Lorenz 225-247, ThomasLabyrinth 250-288, FHN_PDE 291-398,
-Burgers 402-459).  DiffReact (463-577) is not in the BASELINE configs and is not built.
+Burgers 402-459, DiffReact 463-577): all ten of the reference's systems.
 """
 import ctypes
 
@@ -174,3 +174,22 @@ class Burgers(ODE):
         x_fine = np.linspace(-1, 1, num=(d_x - 1) + 1)
         u0 = 0.5 * (np.cos(4.5 * np.pi * x_fine) + 1)
         super().__init__(f'Burgers_{d_x}', mn, mx, u0, param=(float(nu),), **kwargs)
+
+
+class DiffReact(ODE):
+    """2-D diffusion-reaction (FitzHugh-Nagumo reaction, PDEBench) on a d_x x d_x grid with zero-flux
+    walls, d = 2 d_x^2, state u | v (systems.py:463-577); param = (Du, Dv, k).  The propagator holds
+    one slice per workgroup, so 3 <= d_x <= 32 (larger grids are refused by the library)."""
+    kind = _lib.SYS_DIFFREACT
+
+    def __init__(self, d_x: int, Du: float = 1e-3, Dv: float = 5E-3, k: float = 5E-3, seed=45, **kwargs):
+        self.d_x = d_x
+        self.d_y = d_x
+        self.Du = Du
+        self.Dv = Dv
+        self.k = k
+        d = 2 * (d_x * d_x)
+        self.nx = d_x
+        mn, mx = np.array([[-4] * d, [4] * d])
+        u0 = np.random.default_rng(seed).uniform(size=d)
+        super().__init__(f'DiffReact2D_{d_x}', mn, mx, u0, param=(float(Du), float(Dv), float(k)), **kwargs)
