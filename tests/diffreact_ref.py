@@ -13,20 +13,25 @@ TABLEAUX = {
 }
 
 
-def rk_np(f, order, t0, t1, steps, u0, mode='fixed'):
+def rk_np(f, order, t0, t1, steps, u0, mode='fixed', gsteps=None, j0=0):
     """`steps` steps of tableau `order` from t0 to t1; mode 'fixed': h = (t1-t0)/steps, 'linspace':
-    h_n = t[n+1]-t[n] on t[j] = j*dt + t0, t[steps] = t1 (LinGrid)."""
+    h_n = t[n+1]-t[n] on t[j] = j*dt + t0, t[steps] = t1 (LinGrid).  With gsteps (linspace only):
+    steps j0 .. j0+steps-1 of the global grid of gsteps steps over [t0, t1] (nngp_rk_batch_grid)."""
     A, B = TABLEAUX[order]
     S = len(B)
     t0, t1 = np.float64(t0), np.float64(t1)
-    dt = (t1 - t0) / np.float64(steps)
+    if gsteps is None:
+        gsteps = steps
+    else:
+        assert mode == 'linspace'
+    dt = (t1 - t0) / np.float64(gsteps)
     u = np.array(u0, dtype=np.float64)
-    jd = np.float64(0.0)
+    jd = np.float64(j0)
     tn = jd * dt + t0
     for n in range(steps):
         if mode == 'linspace':
             jd = jd + np.float64(1.0)
-            tn1 = t1 if n == steps - 1 else jd * dt + t0
+            tn1 = t1 if n == gsteps - 1 - j0 else jd * dt + t0
             h = tn1 - tn
             tn = tn1
         else:

@@ -1,4 +1,6 @@
 """Pairs (oracle System, product ODE factory) for every fixture key in tests/golden/rhs.npz and rk.npz."""
+import numpy as np
+
 import oracle as O
 
 
@@ -36,6 +38,49 @@ def product_ode(g, key):
         'fhnpde10_n': lambda: g.FHN_PDE(d_x=10, normalization='-11'),
         'fhnpde4': lambda: g.FHN_PDE(d_x=4),
     }[key]()
+
+
+# the seven ODE systems: oracle name -> (product class, param); both normalisations
+ODE_SYSTEMS = {
+    'lorenz': ('Lorenz', ()),
+    'hopf': ('Hopf', (500.0,)),
+    'tomlab': ('ThomasLabyrinth', ()),
+    'fhn_ode': ('FHN_ODE', ()),
+    'rossler': ('Rossler', ()),
+    'brus': ('Brusselator', ()),
+    'dblpend': ('DblPend', ()),
+}
+
+
+def oracle_ode(name, norm):
+    """Oracle System of one ODE: the '-11' wrapper (norm) or the identity system."""
+    return O.System(name, normalized=bool(norm), param=ODE_SYSTEMS[name][1])
+
+
+def product_ode_norm(g, name, norm):
+    cls = getattr(g, ODE_SYSTEMS[name][0])
+    return cls(normalization='-11') if norm else cls()
+
+
+def oracle_burgers(d, norm, dense=False, nu=0.01):
+    if norm:
+        return O.System('burgers', d=d, param=(nu,), mn=0, mx=1, dense=dense)
+    return O.System('burgers', d=d, param=(nu,), normalized=False, dense=dense)
+
+
+def product_burgers(g, d, norm, nu=0.01):
+    return g.Burgers(d_x=d, nu=nu, normalization='-11') if norm else g.Burgers(d_x=d, nu=nu)
+
+
+def burgers_u0(d):
+    """Burgers' physical initial condition (systems.py:402-459), as the product computes it"""
+    return 0.5 * (np.cos(4.5 * np.pi * np.linspace(-1, 1, num=d)) + 1)
+
+
+def burgers_h(d, nu=0.01):
+    """a step inside the explicit stability limit of the d-point grid: min(0.1 dx^2/nu, 0.1 dx)"""
+    dx = 2.0 / (d - 1)
+    return min(0.1 * dx * dx / nu, 0.1 * dx)
 
 
 KEYS = ['lorenz', 'hopf', 'tomlab', 'fhn_ode', 'rossler', 'brus', 'dblpend', 'lorenz_id', 'burgers128',
