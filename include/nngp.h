@@ -114,6 +114,21 @@ int nngp_rk_batch_grid(const nngp_system *sys, int tableau, int n_slices, const 
                        const double *g1, int64_t gsteps, const int64_t *j0, int64_t steps,
                        const double *u0, double *uF, void *stream);
 
+/* Sampled trajectory of every slice in ONE launch (replaces SolverRK.run_F_full / run_G_full,
+ * solver.py:109-113 -> RK.run RK.py:91-99, as called per slice by Parareal._build_cont_traj,
+ * parareal.py:500-508).  Slice i integrates `steps` steps from u0[i] exactly as nngp_rk_batch
+ * would with the same tableau and step_mode, and writes
+ *     traj[i][0] = u0[i],   traj[i][p] = state after min(p*every, steps) steps,  p = 1..n_out-1,
+ *     n_out = 1 + ceil(steps / every)
+ * so every row is bitwise what nngp_rk_batch returns after that many steps of the same grid, and
+ * with NNGP_STEP_FIXED the last row is bitwise its end state.  Both step modes, with and without
+ * NNGP_STEP_CONTRACT; the paging quirk does not apply (RK.run never pages).  Each shape runs on
+ * the kernel form its nngp_rk_batch launch would use.
+ * traj: DEVICE [n_slices][n_out][sys->d], must not alias u0.  every >= 1. */
+int nngp_rk_traj(const nngp_system *sys, int tableau, int step_mode, int n_slices,
+                 const double *t0, const double *t1, int64_t steps, int64_t every,
+                 const double *u0, double *traj, void *stream);
+
 /* Vector field evaluation f_n(u) for n states (what ODE.get_vector_field() returns as a
  * callable, systems.py:32-44).  u, out: DEVICE [n][sys->d].                                 */
 int nngp_rhs_batch(const nngp_system *sys, int n, const double *u, double *out, void *stream);

@@ -1,5 +1,5 @@
-// nngp_rk_dev.h -- device building blocks of the RK propagators, shared by nngp_rk.hip (the
-// batched F/G kernels, exact and contracted builds) and nngp_gp.hip (the fused correction chain,
+// nngp_rk_dev.h -- device building blocks of the RK propagators, shared by nngp_rk_kernels.h (the
+// batched F/G kernels of nngp_rk.hip and nngp_rk_traj.hip, exact and contracted builds) and nngp_gp.hip (the fused correction chain,
 // whose in-kernel G step must be bitwise the G launch).  Included INSIDE
 // `namespace nngp { inline namespace <variant> {`; needs common.h, nngp_math.h and tableau.h.
 #pragma once
@@ -236,14 +236,58 @@ __device__ __forceinline__ double wave_next(double v) {   // lane i <- lane i+1 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Sampled trajectories (nngp_rk_traj, include/nngp.h): the TRAJ instantiation of a propagator
+// writes its slice's rows
+//     out[0] = u0,  out[p] = state after min(p*every, steps) steps,  p = 1 .. n_out-1,
+//     n_out = 1 + ceil(steps / every)
+// instead of the end state alone.  The step loop keeps a countdown (a scalar decrement and branch
+// per step, no modulo), the threads that hold the state in registers store it when the countdown
+// runs out, and the state after the last step goes to row n_out-1 unconditionally after the loop
+// (again, bitwise the same, when every divides steps).  TRAJ is a compile-time parameter: the
+// end-state instantiations contain none of this.
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ __forceinline__ int64_t traj_rows(int64_t steps, int64_t every) {
+    return 1 + (steps + every - 1) / every;
+}
+
+struct TrajOut {
+    double *next, *last;   // the row of the next sample, row n_out-1
+    size_t stride;         // doubles per row (the system's d)
+    int64_t every, left;
+    // base: the slice's [n_out][d] block, whose row 0 the caller writes from the loaded u0
+    __device__ __forceinline__ void init(double *base, int64_t steps, int64_t every_, int d) {
+        stride = (size_t)d;
+        every = left = every_;
+        next = base + stride;
+        last = base + (size_t)(traj_rows(steps, every_) - 1) * stride;
+    }
+    // once after every step: whether that step's state is a sample (wave-uniform: a scalar
+    // countdown and branch); if so, take() is the row to store it to
+    // Marked unlikely so that the store lies out of line and the usual step falls through: with
+    // one wave per SIMD a taken branch is paid in full.
+    __device__ __forceinline__ bool due() {
+        if (__builtin_expect(--left != 0, 1)) return false;
+        left = every;
+        return true;
+    }
+    __device__ __forceinline__ double *take() {
+        double *row = next;
+        next += stride;
+        return row;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
 // Per-slice bodies.  The batched kernels (nngp_rk.hip) call them with their slice's row; the
 // correction chain (nngp_gp.hip) calls them for its in-kernel G step, so both are the same code.
 // ---------------------------------------------------------------------------------------------
 
-// one lane integrates one ODE slice (rk_lane_kernel): u0/uF are the slice's [D] rows
-template <int SYS, int ORDER, bool LINSPACE, bool NORM>
+// one lane integrates one ODE slice (rk_lane_kernel): u0/uF are the slice's [D] rows; TRAJ: uF is
+// the slice's [n_out][D] block, sampled every `every` steps (TrajOut)
+template <int SYS, int ORDER, bool LINSPACE, bool NORM, bool TRAJ = false>
 __device__ __forceinline__ void lane_slice(LaneArgs args, double T0, double T1, int64_t steps, int64_t gsteps,
-                                           int64_t j0, const double *__restrict__ u0, double *__restrict__ uF) {
+                                           int64_t j0, const double *__restrict__ u0, double *__restrict__ uF,
+                                           int64_t every = 0) {
     using T = Tableau<ORDER>;
     constexpr int S = T::S;
     constexpr int D = LaneSys<SYS>::D;
@@ -258,6 +302,13 @@ __device__ __forceinline__ void lane_slice(LaneArgs args, double T0, double T1, 
     double u[D], k[S * D], tmp[D];
 #pragma unroll
     for (int c = 0; c < D; c++) u[c] = u0[c];
+    TrajOut tr;
+    if constexpr (TRAJ) {
+        tr.init(uF, steps, every, D);
+#pragma unroll
+        for (int c = 0; c < D; c++) uF[c] = u[c];
+        uF = tr.last;
+    }
     const double dt = (T1 - T0) / (double)(LINSPACE ? gsteps : steps);
     LinGrid grid;
     if constexpr (LINSPACE) grid.init(j0, gsteps, T0, dt);
@@ -274,6 +325,13 @@ __device__ __forceinline__ void lane_slice(LaneArgs args, double T0, double T1, 
         }
 #pragma unroll
         for (int c = 0; c < D; c++) u[c] = step_update<T, D>(u[c], k, c);   // RK.py:170
+        if constexpr (TRAJ) {
+            if (tr.due()) {
+                double *row = tr.take();
+#pragma unroll
+                for (int c = 0; c < D; c++) row[c] = u[c];
+            }
+        }
     }
 #pragma unroll
     for (int c = 0; c < D; c++) uF[c] = u[c];
@@ -282,10 +340,11 @@ __device__ __forceinline__ void lane_slice(LaneArgs args, double T0, double T1, 
 // one wave integrates one Burgers slice, d = 64*EPT (rk_burgers_wave_kernel): lane l owns the
 // contiguous elements l*EPT .. l*EPT+EPT-1; u0/uF are the slice's [d] rows.  Every lane of the
 // wave must be active (the stencil's outer neighbours are wave_ror/wave_rol DPP moves).
-template <int ORDER, bool LINSPACE, int EPT, bool NORM>
+// TRAJ: uF is the slice's [n_out][d] block, sampled every `every` steps (TrajOut).
+template <int ORDER, bool LINSPACE, int EPT, bool NORM, bool TRAJ = false>
 __device__ __forceinline__ void burgers_wave_slice(const FieldArgs &fa, int l, double T0, double T1, int64_t steps,
                                                    int64_t gsteps, int64_t j0, const double *__restrict__ u0,
-                                                   double *__restrict__ uF) {
+                                                   double *__restrict__ uF, int64_t every = 0) {
     using T = Tableau<ORDER>;
     constexpr int S = T::S;
     constexpr int d = 64 * EPT;
@@ -297,6 +356,13 @@ __device__ __forceinline__ void burgers_wave_slice(const FieldArgs &fa, int l, d
         mn[r] = NORM ? fa.norm[e] : 0.0;
         w[r] = NORM ? 0.5 * fa.norm[d + e] : 1.0;   // (mx-mn)/2, see lane_rhs
         sc[r] = NORM ? fa.norm[2 * d + e] : 1.0;
+    }
+    TrajOut tr;
+    if constexpr (TRAJ) {
+        tr.init(uF, steps, every, d);
+#pragma unroll
+        for (int r = 0; r < EPT; r++) uF[l * EPT + r] = u[r];
+        uF = tr.last;
     }
     const bool first = l == 0, last = l == 63;     // rows 0 and d-1 live in lanes 0 and 63
     const double cxx = fa.c_off, cdg = fa.c_diag, q = fa.c_grad;
@@ -336,6 +402,13 @@ __device__ __forceinline__ void burgers_wave_slice(const FieldArgs &fa, int l, d
         }
 #pragma unroll
         for (int r = 0; r < EPT; r++) u[r] = step_update<T, EPT>(u[r], k, r);   // RK.py:170
+        if constexpr (TRAJ) {
+            if (tr.due()) {
+                double *row = tr.take();
+#pragma unroll
+                for (int r = 0; r < EPT; r++) row[l * EPT + r] = u[r];
+            }
+        }
     }
 #pragma unroll
     for (int r = 0; r < EPT; r++) uF[l * EPT + r] = u[r];

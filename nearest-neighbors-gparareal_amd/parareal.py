@@ -321,6 +321,44 @@ class Parareal():
         self.runs[cstm_mdl_name or mdl.name] = out
         return out
 
+    # --------------------------------------------------------------------------- trajectory
+    def build_cont_traj(self, key=None, every=1, return_t=False):
+        """The solution between the slice boundaries (parareal.py:487-508): the fine solver's
+        trajectory of every slice from the run's last iterate.  `key` is a run's name in self.runs
+        or a dict with 't' and 'u'; `every` keeps every every-th fine step (and each slice's last).
+        Returns the reference's np.vstack of the per-slice blocks, [N * n_out][n] with n_out =
+        SolverRK.traj_rows(Nf, every): block i starts at u[i], and its last row is the fine
+        solution at t[i+1] (so the boundaries appear twice, as in the reference).  return_t=True
+        also returns the rows' time stamps."""
+        if key is None:
+            if len(self.runs) != 1:
+                raise Exception('Multiple runs, must specify key')
+            key = list(self.runs.keys())[0]
+        if isinstance(key, dict) and 't' in key and 'u' in key:
+            t, u = key['t'], key['u']
+        else:
+            t, u = self.runs[key]['t'], self.runs[key]['u']
+        return self._build_cont_traj(t, u, every=every, return_t=return_t)
+
+    def _build_cont_traj(self, t, u, every=1, return_t=False):
+        """parareal.py:500-508 (and :1063-1071 for PararealLight's 2-D u), with the N calls of
+        solver.run_F_full as ONE launch on RK.run's np.linspace grid."""
+        torch = _lib.require_gpu()
+        solver, N = self.solver, self.N
+        t, u = np.asarray(t, dtype=np.float64), np.asarray(u, dtype=np.float64)
+        starts = u[:N, :, -1] if u.ndim == 3 else u[:N, :]
+        U0 = torch.tensor(np.ascontiguousarray(starts), device='cuda')
+        try:
+            traj = solver.run_F_traj_batch(t[:N], t[1:N + 1], U0, every=every, step_mode='linspace')
+        except torch.cuda.OutOfMemoryError as e:
+            rows = solver.traj_rows(solver.Nf, every)
+            raise ValueError(f'the trajectory of {N} slices x {rows} rows x {U0.shape[1]} doubles does not fit '
+                             f'the device at every={every}: pass a larger every') from e
+        out = traj.reshape(-1, U0.shape[1]).cpu().numpy()
+        if return_t:
+            return out, np.concatenate([solver.traj_times(t[i], t[i + 1], solver.Nf, every) for i in range(N)])
+        return out
+
     # ------------------------------------------------------------------------------ reports
     def _fine_reference(self):
         """The serial fine solve the reports compare against (parareal.py:636-643): run_F_timed

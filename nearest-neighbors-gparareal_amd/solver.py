@@ -5,6 +5,8 @@ Single-slice calls (`run_F(t0, t1, u0)`, `run_G`, their `_timed` variants) keep 
 signatures and numpy in/out.  The Parareal driver uses the batched device entry points
 `run_F_batch` / `run_G_batch`, which integrate every slice of one iteration in ONE kernel launch
 (nngp_rk_batch); that replaces `pool.map(solver.run_F_timed, ...)` at parareal.py:310-315.
+`run_F_traj_batch` / `run_G_traj_batch` return every slice's sampled trajectory from one launch
+(nngp_rk_traj); `run_F_full` / `run_G_full` (RK.run, numpy in/out) are built on it.
 
 Step conventions (include/nngp.h):
   step_mode='fixed'    (default)  h = (t1-t0)/steps            RK.run_get_last, RK.py:101-109
@@ -164,30 +166,73 @@ class SolverRK(SolverAbstr):
     def run_G(self, t0, t1, u0):
         return self._single(self.G, self.Ng, t0, t1, u0)
 
-    def _full(self, method, steps, t0, t1, u0):
-        """Whole trajectory on the np.linspace grid (RK.run, RK.py:91-99): one launch per point."""
-        torch = _lib.require_gpu()
-        steps = int(steps)
-        t = np.linspace(t0, t1, num=steps + 1)
-        out = np.empty((steps + 1, len(u0)))
-        out[0] = u0
-        cur = torch.tensor(np.asarray(u0, dtype=np.float64).reshape(1, -1), device='cuda')
-        nxt = torch.empty_like(cur)
-        mode = self.step_mode
-        self.step_mode = _lib.STEP_FIXED | (mode & _lib.STEP_CONTRACT)
-        try:
-            for n in range(steps):
-                ta = torch.tensor([t[n]], dtype=torch.float64, device='cuda')
-                tb = torch.tensor([t[n + 1]], dtype=torch.float64, device='cuda')
-                self._launch(method, ta, tb, 1, cur, nxt, None)
-                cur, nxt = nxt, cur
-                out[n + 1] = cur[0].cpu().numpy()
-        finally:
-            self.step_mode = mode
+    # -------------------------------------------------------------------------- trajectories
+    @staticmethod
+    def traj_rows(steps, every):
+        """Rows of a sampled trajectory: the start, every `every`-th step, and the last step."""
+        steps, every = int(steps), int(every)
+        return 1 + -(-steps // every)
+
+    @staticmethod
+    def traj_times(t0, t1, steps, every):
+        """Time stamps of a sampled trajectory's rows: np.linspace(t0, t1, steps + 1) (RK.run,
+        RK.py:91-99) at the step counts 0, every, 2*every, ..., steps."""
+        steps, every = int(steps), int(every)
+        idx = np.minimum(np.arange(SolverRK.traj_rows(steps, every)) * every, steps)
+        return np.linspace(t0, t1, num=steps + 1)[idx]
+
+    def _traj_batch(self, method, steps, t0, t1, U0, every, out, stream, step_mode=None):
+        """Every slice's sampled trajectory in ONE launch (nngp_rk_traj): out[i, p] is the state of
+        slice i after min(p*every, steps) steps from U0[i], out[i, 0] = U0[i]."""
+        import torch
+        steps, every = int(steps), int(every)
+        if every < 1:
+            raise ValueError(f'every must be >= 1 (got {every})')
+        n, d = U0.shape
+        n_out = self.traj_rows(steps, every)
+        if out is None:
+            out = torch.empty((n, n_out, d), dtype=torch.float64, device=U0.device)
+        assert tuple(out.shape) == (n, n_out, d) and out.dtype == torch.float64 and out.is_contiguous()
+        if n == 0:
+            return out
+        assert U0.dtype == torch.float64 and U0.is_contiguous() and U0.is_cuda and out.is_cuda
+        if not torch.is_tensor(t0):
+            t0 = torch.tensor(np.asarray(t0, dtype=float), device=U0.device)
+            t1 = torch.tensor(np.asarray(t1, dtype=float), device=U0.device)
+        cs = self.f.csystem(U0.device)
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        mode = self.step_mode if step_mode is None else step_mode
+        _lib.check(_lib.lib().nngp_rk_traj(ctypes.byref(cs), _lib.TABLEAU[method], mode, n, t0.data_ptr(),
+                                            t1.data_ptr(), steps, every, U0.data_ptr(), out.data_ptr(), st))
         return out
 
-    def run_F_full(self, t0, t1, u0):
-        return self._full(self.F, self.Nf, t0, t1, u0)
+    def _traj_mode(self, step_mode):
+        if step_mode is None:
+            return None
+        return ({'fixed': _lib.STEP_FIXED, 'linspace': _lib.STEP_LINSPACE}[step_mode] |
+                (self.step_mode & _lib.STEP_CONTRACT))
 
-    def run_G_full(self, t0, t1, u0):
-        return self._full(self.G, self.Ng, t0, t1, u0)
+    def run_F_traj_batch(self, t0, t1, U0, every=1, out=None, stream=None, step_mode=None):
+        """(n, d) device states -> (n, traj_rows(Nf, every), d) device trajectories of the fine
+        solver in one launch, in the solver's own step_mode and fma: with 'fixed' steps the last
+        row is bitwise run_F_batch's end state.  step_mode='linspace' walks np.linspace(t0, t1,
+        Nf + 1) instead, as RK.run does (run_F_full, Parareal.build_cont_traj)."""
+        return self._traj_batch(self.F, self.Nf, t0, t1, U0, every, out, stream, self._traj_mode(step_mode))
+
+    def run_G_traj_batch(self, t0, t1, U0, every=1, out=None, stream=None, step_mode=None):
+        return self._traj_batch(self.G, self.Ng, t0, t1, U0, every, out, stream, self._traj_mode(step_mode))
+
+    def _full(self, method, steps, t0, t1, u0, every=1):
+        """Trajectory on the np.linspace grid (RK.run, RK.py:91-99), every `every`-th point of it:
+        one launch in LINSPACE mode, whose step n is h = t[n+1] - t[n] of that grid."""
+        torch = _lib.require_gpu()
+        U0 = torch.tensor(np.asarray(u0, dtype=np.float64).reshape(1, -1), device='cuda')
+        out = self._traj_batch(method, steps, np.array([t0], dtype=float), np.array([t1], dtype=float), U0, every,
+                               None, None, self._traj_mode('linspace'))
+        return out[0].cpu().numpy()
+
+    def run_F_full(self, t0, t1, u0, every=1):
+        return self._full(self.F, self.Nf, t0, t1, u0, every)
+
+    def run_G_full(self, t0, t1, u0, every=1):
+        return self._full(self.G, self.Ng, t0, t1, u0, every)
