@@ -51,7 +51,9 @@ __global__ void __launch_bounds__(64) rk_lane_kernel(LaneArgs args, int n_slices
 // Hopf since then (GroupSys<HOPF> below): registers carried across stages (85
 // VALU), one fused `v_fmac_f64_dpp` per RHS and RK4's third stage re-using the second's u2/mu
 // (78), and two steps per loop iteration (the taken branch of a one-step loop is paid in full
-// with one wave per SIMD): 0.1725 -> 0.158 us/step (profiles/r07/bench_before_after.txt).
+// with one wave per SIMD): 0.1725 -> 0.158 us/step (profiles/r07/bench_before_after.txt); then
+// RK4's three u2/mu divisions per step as one, in spare lanes of the component's bank (73), and
+// four steps per iteration: 0.143 us/step (profiles/r08/bench_before_after.txt).
 // Bitwise the lane kernel: each component is rounded by the same expression in the same order.
 // ---------------------------------------------------------------------------------------------
 template <int CTRL>
@@ -135,9 +137,10 @@ template <> struct GroupSys<NNGP_SYS_HOPF> {     // systems.py:148-154, as LaneS
 #else
     struct St {
         double Q, A2, B2, P, S, M;
+        double OFF, q;   // the lane-batched form's (f_batched below); unused otherwise
     };
     __device__ static St init(int c) {
-        return St{0.0, 0.0, 0.0, c == 2 ? 1.0 : 0.0, c == 0 ? -1.0 : 1.0, -1.0};
+        return St{0.0, 0.0, 0.0, c == 2 ? 1.0 : 0.0, c == 0 ? -1.0 : 1.0, -1.0, -0.0, 0.0};
     }
     // q = x/mu (div_const) and sq = x*x in every lane, then P, Q, B2 in an order that leaves two
     // instructions between each register's write and its DPP read: q -> (sq, P) -> Q;
@@ -185,6 +188,59 @@ template <> struct GroupSys<NNGP_SYS_HOPF> {     // systems.py:148-154, as LaneS
         }
         return o;
     }
+    // Lane-batched u2/mu (RK4 in fixed-step mode: group_batch_slots below).
+    // Bank 2's f is the constant 1, so k2 = h*sc2 is the same at every stage of every step of the
+    // slice, and the time inputs of stages 1..S-1 -- u2 + RN(a*k2), one `a` per stage, two distinct
+    // ones in RK4 -- are known when the step starts.  Bank 2 has four lanes and needs one: lane 8
+    // keeps the component, lanes 9 and 10 get the two offsets added to stage 0's input (OFF: a*k2
+    // there, -0.0 in every other lane, and x + (-0.0) is x bit for bit, zeros of either sign and NaN
+    // included), run stage 0's own de-normalisation and division on them -- the roundings of the
+    // reference's later stages, one lane over -- and stage 0's q register, carried, holds all three
+    // quotients.  Stages 1..3 then take theirs with the move they need anyway (row_newbcast:9, 9
+    // and 10 instead of 8) and skip the division: 12 + 9 + 9 + 9 VALU and no s_nop.  The state u is
+    // not touched: lanes 9 and 10 of stage 0 feed nothing but q (their g is +-0 and their f is 1 for
+    // any finite x), so lanes 9..11 keep carrying lane 8's u2.
+    // Wait states of a take stage (every VGPR a DPP op reads written at least two instructions
+    // earlier): x may be written by the instruction before the statement, so its first DPP read is
+    // the third op, behind x*x and the move of the carried q; q was written by stage 0's statement
+    // and Q by the previous statement's fused op, which its three-op tail follows, and nothing
+    // between two statements writes either (no other code names them); sq -> (Q, P) -> B2;
+    // Q -> (P, B2) -> fused; P -> (B2, fused) -> P.
+    __device__ static void batch_init(St &s, int lane, double off0, double off1) {
+        s.OFF = lane == 9 ? off0 : lane == 10 ? off1 : -0.0;
+        // opaque from here on, so that the step's u + OFF stays one add: x + (-0.0) -> x is a legal
+        // fold that would move the add into the select, per step (the present compiler gives the
+        // same loop without this)
+        asm("" : "+v"(s.OFF));
+    }
+#define NNGP_HOPF_TAKE(L)                                                          \
+    asm("v_mul_f64 %[sq], %[x], %[x]\n\t"                                          \
+        "v_mov_b64_dpp %[Q], %[q] row_newbcast:" L " row_mask:0xf bank_mask:0x3\n\t" \
+        "v_mov_b64_dpp %[P], %[x] row_newbcast:4 row_mask:0xf bank_mask:0x1\n\t"    \
+        "v_mov_b64_dpp %[B2], %[sq] row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"  \
+        "v_fmac_f64_dpp %[Q], %[sq], %[M] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t" \
+        "v_mov_b64_dpp %[P], %[x] row_newbcast:0 row_mask:0xf bank_mask:0x2\n\t"    \
+        NNGP_HOPF_TAIL("Q")                                                        \
+        : [o] "=&v"(o), [sq] "=&v"(sq), [t] "=&v"(t), [Q] "+v"(s.Q), [B2] "+v"(s.B2), [P] "+v"(s.P) \
+        : [x] "v"(x), [q] "v"(s.q), [S] "v"(s.S), [M] "v"(s.M))
+    // slot: -1 = stage 0 (divides in every lane), 0 / 1 = the quotient of lane 9 / 10
+    __device__ static double f_batched(double x, St &s, int slot, const LaneArgs &a) {
+        double o, sq, e, t;
+        if (slot < 0) {
+            asm(NNGP_HOPF_HEAD
+                "v_fmac_f64_dpp %[Q], %[sq], %[M] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"
+                NNGP_HOPF_TAIL("Q")
+                : [o] "=&v"(o), [sq] "=&v"(sq), [t] "=&v"(t), [e] "=&v"(e), [q] "=&v"(s.q), [Q] "+v"(s.Q),
+                  [B2] "+v"(s.B2), [P] "+v"(s.P)
+                : [x] "v"(x), [S] "v"(s.S), [M] "v"(s.M), [b] "v"(a.param[0]), [r] "v"(a.rparam0));
+        } else if (slot == 0) {
+            NNGP_HOPF_TAKE("9");
+        } else {
+            NNGP_HOPF_TAKE("10");
+        }
+        return o;
+    }
+#undef NNGP_HOPF_TAKE
 #undef NNGP_HOPF_HEAD
 #undef NNGP_HOPF_TAIL
 #endif
@@ -280,11 +336,87 @@ static_assert(group_stage_repeats<Tableau<4>>(2) && group_repeat_count<Tableau<4
 static_assert(group_repeat_count<Tableau<1>>() == 0 && group_repeat_count<Tableau<2>>() == 0 &&
               group_repeat_count<Tableau<8>>() == 0, "RK1, RK2, RK8: no stage repeats");
 
-// stage s of the group RHS: a field with carried state (St) is told whether the stage repeats and
-// whether the next one will (never both: what a stage keeps, the next uses up)
-template <int SYS, typename T, typename G>
+// Lane batching of a component whose f is the same constant at every stage (all its k_j bitwise
+// equal, k): its input at stage 0 is u, and at a stage whose tableau row has a single non-zero
+// entry a it is u + RN(a*k) whichever k_j the entry is on, so what a group RHS derives from those
+// inputs can be computed for all of them at stage 0, in spare lanes of the component's bank (slot =
+// the index of a among the tableau's distinct such entries, in order of appearance; a repeating
+// stage has its predecessor's).  group_batch_slot: -1 for stage 0, the slot, or -2 where the input
+// has another form (a later row with none or several entries).  A group RHS with an f_batched
+// batches when the tableau has exactly the two slots the form is built for: RK4 (a = 1/2 at
+// stages 1 and 2, a = 1 at stage 3); not RK1 and RK2 (no and one slot) nor RK8 (row 2 has two
+// entries), which keep the form above.
+template <typename T>
+__host__ __device__ constexpr double group_batch_entry(int s) {   // the single entry of row s, or 0.0
+    double a = 0.0;
+    for (int j = 0; j < s; j++) {
+        if (T::A[s][j] == 0.0) continue;
+        if (a != 0.0) return 0.0;
+        a = T::A[s][j];
+    }
+    return a;
+}
+template <typename T>
+__host__ __device__ constexpr int group_batch_slot(int s) {
+    if (s == 0) return -1;
+    const double a = group_batch_entry<T>(s);
+    if (a == 0.0) return -2;
+    int slot = 0;   // the distinct entries of the rows before a's first
+    for (int r = 1; group_batch_entry<T>(r) != a; r++) {
+        bool seen = false;
+        for (int q = 1; q < r; q++) seen = seen || group_batch_entry<T>(q) == group_batch_entry<T>(r);
+        slot += !seen;
+    }
+    return slot;
+}
+template <typename T>
+__host__ __device__ constexpr int group_batch_slots() {   // how many slots, -1: not of this form
+    int n = 0;
+    for (int s = 1; s < T::S; s++) {
+        const int slot = group_batch_slot<T>(s);
+        if (slot == -2) return -1;
+        n = slot + 1 > n ? slot + 1 : n;
+    }
+    return n;
+}
+template <typename T>
+__host__ __device__ constexpr double group_batch_coef(int slot) {   // the entry a of a slot
+    for (int s = 1; s < T::S; s++)
+        if (group_batch_slot<T>(s) == slot) return group_batch_entry<T>(s);
+    return 0.0;
+}
+static_assert(group_batch_slots<Tableau<4>>() == 2 && group_batch_slot<Tableau<4>>(1) == 0 &&
+              group_batch_slot<Tableau<4>>(2) == 0 && group_batch_slot<Tableau<4>>(3) == 1 &&
+              group_batch_coef<Tableau<4>>(0) == 0.5 && group_batch_coef<Tableau<4>>(1) == 1.0,
+              "RK4: u + k/2 at stages 1 and 2, u + k at stage 3");
+static_assert(group_batch_slots<Tableau<1>>() == 0 && group_batch_slots<Tableau<2>>() == 1 &&
+              group_batch_slots<Tableau<8>>() == -1, "RK1, RK2, RK8: not lane-batched");
+template <typename T> struct GroupBatchSlots {
+    int slot[T::S];
+};
+template <typename T>
+constexpr GroupBatchSlots<T> group_batch_table() {
+    GroupBatchSlots<T> t{};
+    for (int s = 0; s < T::S; s++) t.slot[s] = group_batch_slot<T>(s);
+    return t;
+}
+template <class GS, typename T, class = void> struct group_batches {
+    static constexpr bool value = false;
+};
+template <class GS, typename T> struct group_batches<GS, T, std::void_t<decltype(&GS::f_batched)>> {
+    static constexpr bool value = group_batch_slots<T>() == 2;
+};
+
+// stage s of the group RHS: a field with carried state (St) is told the stage's slot where it
+// batches (BATCH), else whether the stage repeats and whether the next one will (never both: what
+// a stage keeps, the next uses up)
+template <int SYS, typename T, bool BATCH, typename G>
 __device__ __forceinline__ double group_f(int s, double x, G &gst, double one, const LaneArgs &args) {
     if constexpr (std::is_same_v<G, int>) return GroupSys<SYS>::f(x, gst, one, args);
+    else if constexpr (BATCH) {
+        constexpr GroupBatchSlots<T> tab = group_batch_table<T>();   // a constant once s is unrolled
+        return GroupSys<SYS>::f_batched(x, gst, tab.slot[s], args);
+    }
     else return GroupSys<SYS>::f(x, gst, group_stage_repeats<T>(s), group_stage_repeats<T>(s + 1), args);
 }
 
@@ -346,28 +478,46 @@ __global__ void __launch_bounds__(64) rk_group_kernel(LaneArgs args, int n_slice
             }
         }
     };
+    // Lane batching (group_batch_slots above): fixed-step mode only, where the constant component's
+    // k is the same at every step -- h * (1 * sc), the step's own expressions -- and the per-lane
+    // offsets a*k of the batched stage inputs are set once, here.  (Linspace mode has another h at
+    // every step and keeps the unbatched form.)
+    constexpr bool BATCH = !LINSPACE && group_batches<GroupSys<SYS>, T>::value;
+    if constexpr (BATCH) {
+        double o = one;
+        if constexpr (NORM) o = one * sc;
+        const double kc = dt * o;
+        constexpr double a0 = group_batch_coef<T>(0), a1 = group_batch_coef<T>(1);
+        GroupSys<SYS>::batch_init(gst, tid % 16, a0 * kc, a1 * kc);
+    }
     auto step = [&](int64_t n) __attribute__((always_inline)) {
         const double h = LINSPACE ? grid.next(n, T0, T1, dt) : dt;
 #pragma unroll
         for (int s = 0; s < S; s++) {
-            const double tmp = stage_input<T, 1>(s, u, k, 0);
+            double tmp;
+            if constexpr (BATCH) tmp = s == 0 ? u + gst.OFF : stage_input<T, 1>(s, u, k, 0);
+            else tmp = stage_input<T, 1>(s, u, k, 0);
             double o;
-            if constexpr (NORM) o = group_f<SYS, T>(s, (tmp + 1) * hw + mn, gst, one, args) * sc;
-            else o = group_f<SYS, T>(s, tmp, gst, one, args);
+            if constexpr (NORM) o = group_f<SYS, T, BATCH>(s, (tmp + 1) * hw + mn, gst, one, args) * sc;
+            else o = group_f<SYS, T, BATCH>(s, tmp, gst, one, args);
             k[s] = h * o;
         }
         u = step_update<T, 1>(u, k, 0);
     };
-    // two steps per iteration and a remainder step: the step is one wave's instruction issue with no
-    // other wave on the SIMD to cover the loop's taken branch
+    // UNROLL steps per iteration and a remainder loop: the step is one wave's instruction issue with
+    // no other wave on the SIMD to cover the loop's taken branch.  Four for
+    // the tableaux of up to four stages; RK8's eleven stay at two (code size).
+    constexpr int UNROLL = S <= 4 ? 4 : 2;
     int64_t n = 0;
-    for (; n + 1 < steps; n += 2) {
-        step(n);
-        sample();
-        step(n + 1);
-        sample();
+    for (; n + (UNROLL - 1) < steps; n += UNROLL) {
+#pragma unroll
+        for (int j = 0; j < UNROLL; j++) {
+            step(n + j);
+            sample();
+        }
     }
-    if (n < steps) {
+#pragma unroll 1
+    for (; n < steps; n++) {
         step(n);
         sample();
     }

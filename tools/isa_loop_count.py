@@ -43,7 +43,7 @@ def loop_histogram(kernel='rk_group_kernelILi1ELi4ELb0ELb1E', s=None):
     best = None
     for h in heads:
         label = lines[h].split(':')[0]
-        ends = [k for k, l in enumerate(lines) if label in l and 'branch' in l]
+        ends = [k for k, l in enumerate(lines) if 'branch' in l and l.split()[-1] == label]   # not .LBB1_30 for .LBB1_3
         if not ends:
             continue
         body = lines[h + 1:max(ends) + 1]
