@@ -249,14 +249,16 @@ def knn(X, q, m):
 JITTERS = np.arange(-20, -11, dtype=float)   # models.py:186
 
 
-def predict(X, Y, q, m, theta0, n_restarts=1, fatol=0.1, xatol=0.1, maxfev=400, nthreads=0, return_fits=False):
+def predict(X, Y, q, m, theta0, n_restarts=1, fatol=0.1, xatol=0.1, maxfev=400, nthreads=0, return_fits=False,
+            jitters=None):
+    """jitters: another list of jitter exponents than the reference's JITTERS."""
     X, Y, q, th0 = _c(X), _c(Y), _c(q).reshape(-1), _c(theta0)
     rows, d = X.shape
-    nf = d * len(JITTERS) * n_restarts
+    jit = _c(JITTERS if jitters is None else jitters)
+    nf = d * len(jit) * n_restarts
     assert th0.shape == (nf, 2)
     preds = np.empty(d)
     fits = np.empty((nf, 4))
-    jit = _c(JITTERS)
     rc = lib().orc_predict(_p(X), _p(Y), rows, d, _p(q), int(m), len(jit), _p(jit), int(n_restarts), _p(th0),
                            float(fatol), float(xatol), int(maxfev), _p(preds), _p(fits), int(nthreads))
     assert rc == 0

@@ -196,15 +196,42 @@ SWEEP_CASES = {'r5000': (5000, 0, 5), 'r15000': (15000, 0, 5), 'r600dup': (600, 
 
 
 @functools.lru_cache(maxsize=None)
-def sweep_case(name):
-    """A synthetic correction sweep on Lorenz '-11' (N = 8, I = 0, G = RK1 with 2 steps, m = 18)
-    and the oracle's loop over it, all on the CPU.  The training set is rows//8 points per slice
-    around the fine trajectory with Y = F - G there; UF / UG are the "previous iteration" whose
+def sweep_case(name, m=SWEEP_M):
+    """A synthetic correction sweep on Lorenz '-11' (N = 8, I = 0, G = RK1 with 2 steps, m = 18
+    unless given) and the oracle's loop over it, all on the CPU.  The training set is rows//8 points
+    per slice around the fine trajectory with Y = F - G there; UF / UG are the "previous iteration" whose
     guess chain (nngp_sweep.hip: g[0] = U1[0], g[i+1] = G(g[i]) + (UF[i+1] - UG[i+1])) leaves the
     actual chain at slice 5.  Returns a dict of host arrays and the predicted hit of every slice."""
     import oracle as O
+    D = _sweep_data(name)
+    t, traj, X, Y, UF, UG, th0, per = (D[k] for k in ('t', 'traj', 'X', 'Y', 'UF', 'UG', 'th0', 'per'))
+    N = SWEEP_N
+    so = O.System('lorenz')
+    G = lambda i, u: so.rk(1, t[i], t[i + 1], SWEEP_NG, u)
+    nf = th0.shape[0] // N
+    U1 = np.zeros((N + 1, 3))
+    UG1 = np.zeros((N + 1, 3))
+    U1[0] = traj[0]
+    g = np.zeros((N, 3))
+    g[0] = U1[0]
+    for i in range(N):
+        UG1[i + 1] = G(i, U1[i])
+        U1[i + 1] = O.predict(X, Y, U1[i], m, th0[i * nf:(i + 1) * nf]) + UG1[i + 1]
+        if i + 1 < N:
+            g[i + 1] = G(i, g[i]) + (UF[i + 1] - UG[i + 1])
+    hit = [bool(np.array_equal(O.knn(X, g[i], m)[0], O.knn(X, U1[i], m)[0])) for i in range(N)]
+    ncand_q = [n_candidates(ref_knn(X, U1[i], m)[2], m) for i in range(N)]
+    ncand_g = [n_candidates(ref_knn(X, g[i], m)[2], m) for i in range(N)]
+    return dict(t=t, traj=traj, X=X, Y=Y, UF=UF, UG=UG, th0=th0, U1=U1, UG1=UG1, g=g, hit=hit,
+                ncand_q=ncand_q, ncand_g=ncand_g, rows=per * N, m=m, N=N)
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep_data(name):
+    """The part of a sweep case that does not depend on m: training set, previous iteration, draws."""
+    import oracle as O
     rows, copies, seed = SWEEP_CASES[name]
-    N, m = SWEEP_N, SWEEP_M
+    N = SWEEP_N
     so = O.System('lorenz')
     t = np.linspace(0, 0.4, N + 1)
     F = lambda i, u: so.rk(4, t[i], t[i + 1], SWEEP_NF, u)
@@ -233,19 +260,4 @@ def sweep_case(name):
         UG[i + 1] = G(i, u)
     UF[5] += 0.03
     th0 = draw_thetas(3, N, seed=45)
-    nf = th0.shape[0] // N
-    U1 = np.zeros((N + 1, 3))
-    UG1 = np.zeros((N + 1, 3))
-    U1[0] = traj[0]
-    g = np.zeros((N, 3))
-    g[0] = U1[0]
-    for i in range(N):
-        UG1[i + 1] = G(i, U1[i])
-        U1[i + 1] = O.predict(X, Y, U1[i], m, th0[i * nf:(i + 1) * nf]) + UG1[i + 1]
-        if i + 1 < N:
-            g[i + 1] = G(i, g[i]) + (UF[i + 1] - UG[i + 1])
-    hit = [bool(np.array_equal(O.knn(X, g[i], m)[0], O.knn(X, U1[i], m)[0])) for i in range(N)]
-    ncand_q = [n_candidates(ref_knn(X, U1[i], m)[2], m) for i in range(N)]
-    ncand_g = [n_candidates(ref_knn(X, g[i], m)[2], m) for i in range(N)]
-    return dict(t=t, traj=traj, X=X, Y=Y, UF=UF, UG=UG, th0=th0, U1=U1, UG1=UG1, g=g, hit=hit,
-                ncand_q=ncand_q, ncand_g=ncand_g, rows=per * N, m=m, N=N)
+    return dict(t=t, traj=traj, X=X, Y=Y, UF=UF, UG=UG, th0=th0, per=per)

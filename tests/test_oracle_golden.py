@@ -10,6 +10,7 @@ Tolerances (fp64):
     chaotic Lorenz nnGP: K within +-2 of the reference.
 """
 import ctypes
+import warnings
 
 import numpy as np
 import pytest
@@ -199,6 +200,29 @@ def test_nelder_mead_logic_bit_exact_vs_scipy(maxfev):
                 assert ne == ref.nfev, name
                 assert np.array_equal(th, ref.x), name
                 assert fv == ref.fun or (np.isinf(fv) and np.isinf(ref.fun)), name
+
+
+@pytest.mark.parametrize('maxfev', [1, 2, 3, 4, 5, 6, 9, 10, 11, 400])
+def test_nelder_mead_caps_zero_starts_and_tolerance_edges_vs_scipy(maxfev):
+    """The same at the evaluation caps around the initial simplex and the first iterations, from
+    starts with zero components (the 0.00025 branch of the initial simplex), with tolerance 0 (only
+    the iteration rule ends the fit) and 1e9 (the first check ends it)."""
+    rng = np.random.default_rng(1)
+    for name, fn in _objectives():
+        for zero in ((0,), (1,), (0, 1), ()):
+            th0 = rng.integers(-8, 0, 2).astype(float)
+            th0[list(zero)] = 0.0
+            for tol in (0.0, 0.1, 1e9):
+                if maxfev == 400 and tol == 0.0 and name != 'flat':
+                    continue   # (400 evaluations of a python callback per case; 'flat' keeps the cap)
+                with warnings.catch_warnings():
+                    warnings.simplefilter('ignore')
+                    ref = minimize(fn, th0, method='Nelder-Mead',
+                                   options={'fatol': tol, 'xatol': tol, 'maxfev': maxfev, 'maxiter': maxfev})
+                th, fv, ne = _c_nm(fn, th0, tol, tol, maxfev)
+                assert ne == ref.nfev <= max(maxfev, 1), (name, zero, tol)
+                assert np.array_equal(th, ref.x), (name, zero, tol)
+                assert fv == ref.fun or (np.isinf(fv) and np.isinf(ref.fun)), (name, zero, tol)
 
 
 def test_nm_fits_track_reference():
