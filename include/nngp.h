@@ -342,6 +342,46 @@ int nngp_correction_sweep_sharded_emulated(const nngp_system *sys, int g_tableau
                                            double *gather, size_t gather_elems, int emulate_ranks,
                                            float *g_ms_out, void *stream);
 
+/* ---- 6. ELM correction (RandNet-Parareal; models.ELM / ELM_base, models.py:476-554) -----------
+ * A random-weights network on the m nearest neighbours.  Weights (drawn on the host exactly as
+ * ELM_base.__init__ / _init_obj do, models.py:481-504, C already multiplied by R, :524):
+ *   bias_h DEVICE [res_size], C DEVICE [res_size][n_poly], n_poly = 1 + d + (degree == 2 ? d(d+1)/2 : 0),
+ *   the columns in sklearn's PolynomialFeatures(degree) order: 1, x_0 .. x_{d-1}, x_i x_j for i <= j.
+ * Supported: degree 1 or 2, 1 <= res_size <= 1024, 1 <= d <= 8192, relu, alpha = 0.  The arithmetic
+ * (summation orders, the Gram-Schmidt solve and its threshold) is the contract of DESIGN.md 3.6,
+ * restated in tests/elm_ref.py.
+ *
+ * nngp_elm_hidden: hidden features of a batch of rows,
+ *     H[row][r] = max(0, bias_h[r] + sum_f C[r][f] phi_f(X[row]))    self.loss(bias + C @ x.T),
+ *                                                                    models.py:507-508 and :530-531
+ * X DEVICE [rows][d], H DEVICE [rows][res_size].  A row's bits do not depend on the rows it is
+ * batched with.  rows = 0 is a no-op. */
+int nngp_elm_hidden(const double *X, int64_t rows, int d, int degree, int res_size,
+                    const double *bias_h, const double *C, double *H, void *stream);
+
+/* nngp_elm_predict: one prediction = ELM_base.predict (models.py:521-535), enqueued on `stream`
+ * with no host synchronisation: nngp_knn's m nearest rows of X at new_x (:526-528), their cached
+ * hidden rows H[rows][res_size] (nngp_elm_hidden of X) and targets Y[rows][d], the query's hidden
+ * row (:530-531), and the min-norm interpolation with a free intercept through them
+ * (Ridge(alpha=0).fit / predict, :510-511 and :533-534) evaluated at the query.
+ *   preds_out = the prediction [d] (or NULL);  if bias != NULL also out = preds + bias
+ *   (parareal.py:382).  Requires 1 <= m <= min(16, rows).                                      */
+int nngp_elm_predict(const double *X, const double *Y, const double *H, int64_t rows, int d,
+                     const double *new_x, int m, int degree, int res_size, const double *bias_h,
+                     const double *C, double *preds_out, const double *bias, double *out,
+                     void *stream);
+
+/* nngp_elm_sweep: the sequential sweep of one iteration with the ELM model (parareal.py:359-382),
+ * like nngp_correction_sweep without speculation: for i = I .. N-1
+ *     UG1[i+1] = G(t[i], t[i+1], U1[i])             (nngp_rk_batch, the sweep's own G launch)
+ *     U1[i+1]  = nngp_elm_predict(U1[i]) + UG1[i+1]
+ * all on `stream`.  t, U1, UG1 as in nngp_correction_sweep; g_ms_out: HOST, total device time of
+ * the G launches (ms), or NULL.                                                                */
+int nngp_elm_sweep(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t g_steps,
+                   const double *t, int I, int N, double *U1, double *UG1, const double *X,
+                   const double *Y, const double *H, int64_t rows, int m, int degree, int res_size,
+                   const double *bias_h, const double *C, float *g_ms_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,8 @@ EXPORTS = ['nngp_abi_version', 'nngp_last_error', 'nngp_device_count', 'nngp_rk_
            'nngp_gp_mean', 'nngp_predict', 'nngp_correction_sweep', 'nngp_gpfull_lml', 'nngp_gpfull_fit',
            'nngp_gpfull_mean', 'nngp_predict_range', 'nngp_chain_stats', 'nngp_sweep_late_reruns', 'nngp_shutdown',
            'nngp_comm_available', 'nngp_comm_unique_id', 'nngp_comm_init', 'nngp_comm_size', 'nngp_comm_destroy',
-           'nngp_allgather_states', 'nngp_correction_sweep_sharded', 'nngp_correction_sweep_sharded_emulated']
+           'nngp_allgather_states', 'nngp_correction_sweep_sharded', 'nngp_correction_sweep_sharded_emulated',
+           'nngp_elm_hidden', 'nngp_elm_predict', 'nngp_elm_sweep']
 MODEL_PARAREAL, MODEL_NNGP, MODEL_GPFULL = 0, 1, 2
 
 
@@ -100,6 +101,10 @@ def lib():
                                                          [ctypes.c_size_t, i32, ctypes.POINTER(ctypes.c_float), _vp])
     L.nngp_predict_range.argtypes = [_vp, _vp, i64, i32, _vp, i32, i32, _dp, i32, _vp, i32, i32, dbl, dbl, i32,
                                      _vp, _vp]
+    L.nngp_elm_hidden.argtypes = [_vp, i64, i32, i32, i32, _vp, _vp, _vp, _vp]
+    L.nngp_elm_predict.argtypes = [_vp, _vp, _vp, i64, i32, _vp, i32, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.nngp_elm_sweep.argtypes = [ctypes.POINTER(CSystem), i32, i32, i64, _vp, i32, i32, _vp, _vp, _vp, _vp, _vp, i64,
+                                 i32, i32, i32, _vp, _vp, ctypes.POINTER(ctypes.c_float), _vp]
     for name in EXPORTS:
         if name not in ('nngp_abi_version', 'nngp_last_error', 'nngp_device_count', 'nngp_chain_stats',
                         'nngp_sweep_late_reruns'):

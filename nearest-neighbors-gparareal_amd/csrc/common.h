@@ -60,10 +60,11 @@ void set_error(const char *fmt, ...);
 // speculative sweep's batch buffers, which must outlive the per-slice calls.  Growing a slot
 // frees the old buffer after hipFree's implicit device synchronisation.  Not thread-safe across
 // host threads sharing a device.
-constexpr int N_WS_SLOTS = 10;   // slot 2: the sweep's speculation buffers; 3: full-GP factors; 4: fit queues; 5: parked fits;
+constexpr int N_WS_SLOTS = 12;   // slot 2: the sweep's speculation buffers; 3: full-GP factors; 4: fit queues; 5: parked fits;
                                 // 6: the re-speculation window's batch (slot 1 may still be read by an overlapped batch);
                                 // 7 / 8: the fit queues of the overlapped batch / of the re-speculation window;
-                                // 9: the sharded sweep's zeros (nngp_comm.hip)
+                                // 9: the sharded sweep's zeros (nngp_comm.hip);
+                                // 10 / 11: the ELM prediction's scratch / nngp_elm_hidden's partial sums (nngp_elm.hip)
 void *workspace(size_t bytes, int *err, int slot = 0);
 
 // A prepared coordinate of gp_pre_kernel: alpha rows 0..maxm-1 | c | psy | ok

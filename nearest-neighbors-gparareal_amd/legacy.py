@@ -131,6 +131,9 @@ class Parareal(_Parareal):
         # new_lib's _parareal reads self.Ng / self.Nf / self.F / self.G / self.RK_thresh when it
         # runs (new_lib.py:902-997), and the scalability scripts re-assign them after construction
         # (Hopf.py:68-69: s.Nf = s.Nf * 10000; s.RK_thresh = s.Nf/s.N/scaling)
+        model = args[0] if args else kwargs.get('model', 'parareal')
+        if isinstance(model, str) and model.lower() == 'elm':   # new_lib's driver has no ELM branch
+            raise Exception('Not implemented')
         self._setup_solver()
         return super().run(*args, **kwargs)
 

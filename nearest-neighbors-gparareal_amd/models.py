@@ -605,3 +605,218 @@ class GPjax_p(ModelAbstr):
     def restore_attrs(self, pool):
         self.pool = pool
         self._dev = None
+
+
+# ------------------------------------------------------------------------------------------- ELM
+ELM_MAX_M, ELM_MAX_RES, ELM_MAX_D = 16, 1024, 8192   # csrc/nngp_elm.h
+ELM_SUPPORTED = ("supported: loss='relu', degree 1 or 2, alpha == 0, 1 <= m <= %d, 1 <= res_size <= %d, "
+                 '1 <= d <= %d' % (ELM_MAX_M, ELM_MAX_RES, ELM_MAX_D))
+_ELM_DEVICE_BYTES = 288e9   # an MI355X's HBM, when no device is visible to ask
+
+
+def elm_n_poly(d, degree):
+    """Columns of sklearn's PolynomialFeatures(degree) on d inputs (models.py:492-494)."""
+    return 1 + d + (d * (d + 1) // 2 if degree == 2 else 0)
+
+
+def _elm_check(d, res_size, loss, alpha, degree, m):
+    """Refuse what the GPU ELM does not serve -- before any weights are drawn or GPU work is done."""
+    if loss in ('tanh', 'radbad'):
+        raise NotImplementedError(f"ELM loss={loss!r}: a bitwise exp / tanh needs a shared polynomial; " + ELM_SUPPORTED)
+    if loss != 'relu':
+        raise KeyError(loss)   # the reference's losses[loss] (models.py:487-488)
+    if degree not in (1, 2):
+        raise NotImplementedError(f'ELM degree={degree}; ' + ELM_SUPPORTED)
+    if alpha != 0:
+        raise NotImplementedError(f'ELM alpha={alpha}; ' + ELM_SUPPORTED)
+    if not 1 <= int(m) <= ELM_MAX_M:
+        raise ValueError(f'ELM m={m}; ' + ELM_SUPPORTED)
+    if not 1 <= int(res_size) <= ELM_MAX_RES:
+        raise ValueError(f'ELM res_size={res_size}; ' + ELM_SUPPORTED)
+    if not 1 <= int(d) <= ELM_MAX_D:
+        raise ValueError(f'ELM d={d}; ' + ELM_SUPPORTED)
+    n_poly = elm_n_poly(d, degree)
+    nbytes = 8 * int(res_size) * n_poly
+    total = _ELM_DEVICE_BYTES
+    try:
+        import torch
+        if torch.cuda.is_available():
+            total = torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory
+    except ImportError:
+        pass
+    if nbytes > 0.8 * total:
+        raise ValueError(f'ELM weights C = res_size x n_poly = {res_size} x {n_poly} doubles = {nbytes} bytes do not '
+                         f'fit the device ({int(total)} bytes, at most 80 % for C)')
+
+
+class ELM_base():
+    """The reference's ELM_base (models.py:476-539) on the GPU: a random-weights network
+    relu(bias + C @ PolynomialFeatures(degree)(x)) on the m nearest neighbours, fitted by the
+    min-norm interpolation Ridge(alpha=0) computes.  Same constructor, attributes
+    (bias [res_size][1], C [res_size][n_poly], drawn from default_rng(seed) in the reference's
+    order) and fit / predict / fit_predict on NumPy arrays.  The weights are uploaded once per
+    device (C multiplied by R on the host); the hidden features of the training rows are cached on
+    the device and only computed for rows appended since the last fit."""
+
+    def __init__(self, d, seed=47, res_size=500, loss='relu', M=1, R=1, alpha=0, degree=2, m=5):
+        _elm_check(d, res_size, loss, alpha, degree, m)
+        self.d = d
+        self.N = res_size
+        self.rng = np.random.default_rng(seed)
+        self.m = m
+        self.loss_name = loss
+        self.M = M   # accepted and unused, as in the reference (models.py:522-523)
+        self.R = R
+        self.alpha = alpha
+        self.poly_degree = degree
+        self.degree = elm_n_poly(d, degree)   # the reference keeps n_output_features_ here (models.py:494)
+        self.bias, self.C = self._init_obj()
+        self.x = self.y = None
+        self.k = 0
+        self._weights = {}    # device index -> (bias [res_size], R * C [res_size][n_poly]) tensors
+        self._dev = None      # (X, Y, H, rows): device training set and its hidden rows (H grow-only)
+
+    def _init_obj(self):
+        """models.py:500-504."""
+        N, rng = self.N, self.rng
+        bias = rng.uniform(-1, 1, (N, 1))
+        C = rng.uniform(-1, 1, (N, self.degree))
+        return bias, C
+
+    # ---------------------------------------------------------------------------- device path
+    def weights_device(self, device):
+        import torch
+        key = torch.device(device).index
+        if key not in self._weights:
+            try:
+                self._weights[key] = (torch.tensor(np.ascontiguousarray(self.bias[:, 0]), device=device),
+                                      torch.tensor(np.ascontiguousarray(self.R * self.C), device=device))
+            except torch.cuda.OutOfMemoryError as e:
+                raise ValueError(f'ELM weights C = {self.N} x {self.degree} doubles = {8 * self.N * self.degree} '
+                                 f'bytes do not fit the device') from e
+        return self._weights[key]
+
+    def hidden_device(self, X, out=None, stream=None):
+        """Hidden rows of the device rows X [rows][d] (nngp_elm_hidden)."""
+        import torch
+        bias, C = self.weights_device(X.device)
+        if out is None:
+            out = torch.empty((X.shape[0], self.N), dtype=torch.float64, device=X.device)
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().nngp_elm_hidden(X.data_ptr(), X.shape[0], self.d, self.poly_degree, self.N,
+                                              bias.data_ptr(), C.data_ptr(), out.data_ptr(), st))
+        return out
+
+    def fit_device(self, X, Y):
+        """The driver's device-resident training set (torch tensors [rows][d], append-only between
+        calls: rows the cache already holds are not read again).  H grows by doubling, so steady-state
+        fits allocate nothing."""
+        import torch
+        rows = int(X.shape[0])
+        n0, H = 0, None
+        if self._dev is not None and self._dev[0].device == X.device and rows >= self._dev[3]:
+            H, n0 = self._dev[2], self._dev[3]
+        if H is None or H.shape[0] < rows:
+            grown = torch.empty((max(rows, 2 * (H.shape[0] if H is not None else 32)), self.N),
+                                dtype=torch.float64, device=X.device)
+            if n0:
+                grown[:n0] = H[:n0]
+            H = grown
+        if rows > n0:
+            self.hidden_device(X[n0:rows], out=H[n0:rows])
+        self._dev = (X, Y, H, rows)
+        self.x = self.y = None   # host copies are made on demand (training_set)
+
+    def device_state(self):
+        """(X, Y, H, rows) on the device, uploading a host training set given to fit()."""
+        if self._dev is None:
+            if self.x is None or self.y is None:
+                raise AttributeError("'ELM_base' has no training set yet: call fit(x, y, k) first")
+            x, y = self.x, self.y
+            self.fit_device(_lib.as_device(x), _lib.as_device(y))
+            self.x, self.y = x, y
+        return self._dev
+
+    def training_set(self):
+        """Host (x, y)."""
+        if self.x is None and self._dev is not None:
+            X, Y, _, rows = self._dev
+            return X[:rows].detach().cpu().numpy(), Y[:rows].detach().cpu().numpy()
+        return self.x, self.y
+
+    def predict_device(self, new_x, out=None, bias=None, preds=None, stream=None):
+        """One correction on device tensors (nngp_elm_predict): preds and / or out = preds + bias."""
+        import torch
+        X, Y, H, rows = self.device_state()
+        b, C = self.weights_device(X.device)
+        if preds is None and (out is None or bias is None):
+            preds = torch.empty(self.d, dtype=torch.float64, device=X.device)
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        _lib.check(_lib.lib().nngp_elm_predict(
+            X.data_ptr(), Y.data_ptr(), H.data_ptr(), rows, self.d, new_x.data_ptr(), min(int(self.m), rows),
+            self.poly_degree, self.N, b.data_ptr(), C.data_ptr(), ptr(preds), ptr(bias), ptr(out), st))
+        return preds
+
+    # ------------------------------------------------------------------------- reference API
+    def fit(self, x, y, k):
+        """models.py:515-518."""
+        if hasattr(x, 'data_ptr'):
+            self.fit_device(x, y)
+        else:
+            self.x, self.y = x, y
+            self._dev = None
+        self.k = k
+
+    def predict(self, new_x):
+        """models.py:521-535 (host arrays in, the [d] predicted correction out)."""
+        torch = _lib.require_gpu()
+        q = torch.tensor(np.asarray(new_x, dtype=np.float64).reshape(-1), device='cuda')
+        return self.predict_device(q).cpu().numpy()
+
+    def fit_predict(self, x, y, new_x, k):
+        self.fit(x, y, k)
+        return self.predict(new_x)
+
+
+class ELM(ModelAbstr):
+    """The RandNet-Parareal correction model (models.py:542-554): ELM_base behind the plugin
+    surface, with the driver's device-resident training set and the native sweep."""
+
+    def __init__(self, d, N, seed=47, res_size=20, loss='relu', M=1, R=1, alpha=0, degree=2, m=4, **kwargs):
+        super().__init__(N=N, **kwargs)
+        self.settings = dict(seed=seed, res_size=res_size, loss=loss, M=M, R=R, alpha=alpha, degree=degree, m=m)
+        self.ELM = ELM_base(d=d, **self.settings)
+        self.name = 'ELM'
+        self.n = d
+
+    def fit(self, x, y, k, *args, **kwargs):
+        self.ELM.fit(x, y, k)
+
+    def predict(self, new_x, *args, **kwargs):
+        return self.ELM.predict(new_x)
+
+    def predict_device(self, new_x, out=None, bias=None, preds=None, stream=None):
+        return self.ELM.predict_device(new_x, out=out, bias=bias, preds=preds, stream=stream)
+
+    x = property(lambda self: self.ELM.training_set()[0])
+    y = property(lambda self: self.ELM.training_set()[1])
+
+    def store(self):
+        """A deep copy for the result dict: host x / y, no device tensors."""
+        e = self.ELM
+        x, y = e.training_set()
+        saved = (e._dev, e._weights, e.x, e.y)
+        e._dev, e._weights, e.x, e.y = None, {}, x, y
+        try:
+            new = super().store()
+        finally:
+            e._dev, e._weights, e.x, e.y = saved
+        return new
+
+    def state_dict(self):
+        """The ELM state of a checkpoint is its constructor arguments (the weights follow from the
+        seed); the training set is the checkpoint's x / D."""
+        st = super().state_dict()
+        st['settings'] = dict(self.settings)
+        return st

@@ -26,7 +26,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from .models import JITTERS, MAX_NEIGHBOURS, BareParareal, GPjax_p, NNGP_p
+from .models import ELM, JITTERS, MAX_NEIGHBOURS, BareParareal, GPjax_p, NNGP_p
 from .solver import SolverAbstr
 from .systems import ODE
 
@@ -216,6 +216,13 @@ class Parareal():
         self.shard_corrections = kwargs.get('shard_corrections')
         self.spec_hits = []
 
+    def _world(self):
+        """Ranks of the driver's process group (1 without torch.distributed initialised)."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return 1
+        return dist.get_world_size(self.process_group)
+
     def _get_pool(self, *args, **kwargs):
         pool = kwargs.get('pool', None)
         if pool is None or isinstance(pool, int):
@@ -250,8 +257,12 @@ class Parareal():
             mdl = GPjax_p(n=self.n, N=self.N, worker_pool=kwargs['pool'], **kwargs)
             if 'process_group' not in kwargs:
                 mdl.process_group = self.process_group   # the fits shard over the driver's group
-        elif model.lower() == 'elm':
-            raise NotImplementedError(f'model {model!r} is outside the GParareal/nnGP path (SURVEY.md §7)')
+        elif model.lower() == 'elm':   # parareal.py:94-95; needs no pool
+            if self._world() > 1:
+                raise NotImplementedError("model='elm' runs on one rank: its sweep is a kNN, one small feature "
+                                          'map and a 3x3 solve per slice, with nothing to shard; supported: a '
+                                          'process group of one rank, or none')
+            mdl = ELM(d=self.n, N=self.N, **kwargs)
         else:
             raise Exception('Not implemented')
         s_time = time.time()
@@ -307,6 +318,8 @@ class Parareal():
             mdl = NNGP_p(n=self.n, N=self.N, worker_pool=GpuPool(), **mst['settings'])
         elif mst['name'] == 'GP':
             mdl = GPjax_p(n=self.n, N=self.N, worker_pool=GpuPool(), **mst['settings'])
+        elif mst['name'] == 'ELM':   # its constructor arguments; the training set is the dump's x / D
+            mdl = ELM(d=self.n, N=self.N, **mst['settings'])
         else:
             mdl = BareParareal(N=self.N)
         mdl.load_state(mst)
@@ -476,6 +489,14 @@ class Parareal():
             self.spec_hits.append(int(hits.value))
             if spec < 0 and N - I >= 2 and hits.value < 0.05 * (N - I):
                 self._spec_skip = 7
+        elif isinstance(model, ELM):
+            e = model.ELM
+            Xe, Ye, He, rows_e = e.device_state()
+            be, Ce = e.weights_device(U1.device)
+            _lib.check(lib.nngp_elm_sweep(
+                ctypes.byref(cs), _lib.TABLEAU[solver.G], solver.step_mode, solver.Ng, t_dev.data_ptr(), I, N,
+                U1.data_ptr(), UG1.data_ptr(), Xe.data_ptr(), Ye.data_ptr(), He.data_ptr(), rows_e,
+                min(int(e.m), rows_e), e.poly_degree, e.N, be.data_ptr(), Ce.data_ptr(), ctypes.byref(g_ms), stream))
         elif isinstance(model, GPjax_p):
             Xg, alpha, coef = model._dev
             _lib.check(lib.nngp_correction_sweep(
@@ -581,6 +602,8 @@ class Parareal():
             if isinstance(model, NNGP_p):
                 model.predict_device(X, Y, rows, U1[i], th0[j * nf:(j + 1) * nf], out=U1[i + 1],
                                      bias=UG1[i + 1], preds=P[j], stream=stream)
+            elif isinstance(model, ELM):
+                model.predict_device(U1[i], out=U1[i + 1], bias=UG1[i + 1], preds=P[j], stream=stream)
             else:
                 if isinstance(model, GPjax_p):
                     model.predict_device(U1[i], out=P[j], stream=stream)
@@ -609,7 +632,7 @@ class Parareal():
                 j = i - I
                 model.predict_device(X, Y, rows, U1[i], th0[j * nf:(j + 1) * nf], out=U1[i + 1],
                                      bias=UG1[i + 1], stream=stream)
-            elif isinstance(model, GPjax_p):
+            elif isinstance(model, (GPjax_p, ELM)):
                 model.predict_device(U1[i], out=U1[i + 1], bias=UG1[i + 1], stream=stream)
             else:   # (uF - uG_prev) + uG_new   (models.py:82-83, parareal.py:382)
                 _lib.check(lib.nngp_parareal_update(self.n, UF[i + 1].data_ptr(), UG[i + 1].data_ptr(),
@@ -647,6 +670,10 @@ class Parareal():
         stream = torch.cuda.current_stream().cuda_stream
         ev = _Events(torch)
         is_nngp = isinstance(model, NNGP_p)
+        if isinstance(model, ELM):
+            # the weights' one upload happens here: a host-to-device copy inside the first fit would
+            # wait for the fine sweep queued before it
+            model.ELM.weights_device(dev)
 
         t = np.linspace(tspan[0], tspan[1], num=N + 1)
         t_dev = torch.tensor(t, **f64)
