@@ -55,8 +55,11 @@ enum nngp_system_kind {
     NNGP_SYS_DBL_PEND = 6,          /* systems.py:175-199                                  */
     NNGP_SYS_BURGERS = 7,           /* systems.py:402-459, nx = d, param[0] = nu           */
     NNGP_SYS_FHN_PDE = 8,           /* systems.py:291-398, nx = d_x, d = 2*d_x*d_x         */
-    NNGP_SYS_DIFFREACT = 9          /* systems.py:463-577, nx = d_x (3..32), d = 2*nx*nx, state u | v,
+    NNGP_SYS_DIFFREACT = 9,         /* systems.py:463-577, nx = d_x (3..32), d = 2*nx*nx, state u | v,
                                        param[0..2] = Du, Dv, k; zero-flux walls             */
+    NNGP_SYS_POLY = 10              /* a caller-defined polynomial field (the reference's extension point,
+                                       a subclass of ODE: systems.py:23-61), nx = the table's handle
+                                       from nngp_poly_create, 1 <= d <= 2048                  */
 };
 
 /* Explicit Runge-Kutta tableaux, RK.py:30-48 (value = order). */
@@ -80,7 +83,8 @@ enum nngp_step_mode { NNGP_STEP_FIXED = 0, NNGP_STEP_LINSPACE = 1, NNGP_STEP_CON
 typedef struct nngp_system {
     int32_t kind;        /* enum nngp_system_kind                                         */
     int32_t d;           /* state dimension                                               */
-    int32_t nx;          /* grid points per axis (Burgers: d; FHN_PDE, DIFFREACT: d_x); else 0 */
+    int32_t nx;          /* grid points per axis (Burgers: d; FHN_PDE, DIFFREACT: d_x); POLY: the
+                            table's handle; else 0                                        */
     int32_t normalized;  /* 0: identity, 1: '-11' wrapper                                 */
     double param[4];     /* HOPF: [0]=maxtime (tspan[1]); BURGERS: [0]=nu; DIFFREACT: [0..2]=Du, Dv, k;
                             else unused                                                   */
@@ -132,6 +136,26 @@ int nngp_rk_traj(const nngp_system *sys, int tableau, int step_mode, int n_slice
 /* Vector field evaluation f_n(u) for n states (what ODE.get_vector_field() returns as a
  * callable, systems.py:32-44).  u, out: DEVICE [n][sys->d].                                 */
 int nngp_rhs_batch(const nngp_system *sys, int n, const double *u, double *out, void *stream);
+
+/* Polynomial vector fields (NNGP_SYS_POLY): the right-hand side as data, for systems that are not
+ * one of the compiled kinds (the reference's user subclasses ODE and writes _f_np / _f_jax,
+ * systems.py:23-61).  A table has d rows; row c is the ordered list of the terms
+ * row_ptr[c] .. row_ptr[c+1]-1, term t = coef[t] * u[idx[t][0]] * u[idx[t][1]] * u[idx[t][2]] with
+ * -1 for a factor that is not there (only after the real ones: degree 0..3).  The arithmetic is
+ * fixed: a term is coef times its factors left to right, one rounding per
+ * multiply; a row is its first term plus the following ones in list order; a row without terms is
+ * +0.0.  All arguments are HOST arrays, copied; nothing is launched.
+ *   Checked here, before any HIP call (the kernels trust a registered table): 1 <= d <= 2048,
+ *   0 <= n_terms <= 1048576, row_ptr[0] = 0, non-decreasing, row_ptr[d] = n_terms, every index -1 or
+ *   in [0, d) with no -1 before a real index, every coefficient finite.
+ * *handle_out >= 1 goes into nngp_system.nx of a system of kind NNGP_SYS_POLY with the same d
+ * (param is unused; the '-11' wrapper applies as to every kind).  Every propagator entry point
+ * and nngp_rhs_batch refuses an unknown or destroyed handle and another d with NNGP_E_ARG.  The
+ * device copy is uploaded per device on first use and kept.  nngp_poly_destroy frees a table (its
+ * slot may be handed out again); nngp_shutdown frees all of them.                             */
+int nngp_poly_create(int d, int n_terms, const int32_t *row_ptr_host, const double *coef_host,
+                     const int16_t *idx_host, int32_t *handle_out);
+int nngp_poly_destroy(int32_t handle);
 
 /* Elementwise  out = (a - b) + c   (c may be NULL: out = a - b), n doubles, DEVICE.
  *   Parareal update with the classic model: u = (uF_prev - uG_prev) + uG_new

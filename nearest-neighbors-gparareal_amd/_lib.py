@@ -17,6 +17,7 @@ CSRC = os.path.join(HERE, 'csrc')
 # enums (include/nngp.h)
 SYS_LORENZ, SYS_HOPF, SYS_THOMAS_LABYRINTH, SYS_FHN_ODE, SYS_ROSSLER = 0, 1, 2, 3, 4
 SYS_BRUSSELATOR, SYS_DBL_PEND, SYS_BURGERS, SYS_FHN_PDE, SYS_DIFFREACT = 5, 6, 7, 8, 9
+SYS_POLY = 10
 TABLEAU = {'RK1': 1, 'RK2': 2, 'RK4': 4, 'RK8': 8}
 STEP_FIXED, STEP_LINSPACE, STEP_CONTRACT = 0, 1, 16
 
@@ -27,7 +28,7 @@ EXPORTS = ['nngp_abi_version', 'nngp_last_error', 'nngp_device_count', 'nngp_rk_
            'nngp_gpfull_mean', 'nngp_predict_range', 'nngp_chain_stats', 'nngp_sweep_late_reruns', 'nngp_shutdown',
            'nngp_comm_available', 'nngp_comm_unique_id', 'nngp_comm_init', 'nngp_comm_size', 'nngp_comm_destroy',
            'nngp_allgather_states', 'nngp_correction_sweep_sharded', 'nngp_correction_sweep_sharded_emulated',
-           'nngp_elm_hidden', 'nngp_elm_predict', 'nngp_elm_sweep']
+           'nngp_elm_hidden', 'nngp_elm_predict', 'nngp_elm_sweep', 'nngp_poly_create', 'nngp_poly_destroy']
 MODEL_PARAREAL, MODEL_NNGP, MODEL_GPFULL = 0, 1, 2
 
 
@@ -105,6 +106,8 @@ def lib():
     L.nngp_elm_predict.argtypes = [_vp, _vp, _vp, i64, i32, _vp, i32, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp]
     L.nngp_elm_sweep.argtypes = [ctypes.POINTER(CSystem), i32, i32, i64, _vp, i32, i32, _vp, _vp, _vp, _vp, _vp, i64,
                                  i32, i32, i32, _vp, _vp, ctypes.POINTER(ctypes.c_float), _vp]
+    L.nngp_poly_create.argtypes = [i32, i32, _ip, _dp, ctypes.POINTER(ctypes.c_int16), _ip]
+    L.nngp_poly_destroy.argtypes = [ctypes.c_int32]
     for name in EXPORTS:
         if name not in ('nngp_abi_version', 'nngp_last_error', 'nngp_device_count', 'nngp_chain_stats',
                         'nngp_sweep_late_reruns'):

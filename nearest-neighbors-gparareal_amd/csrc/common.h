@@ -67,6 +67,30 @@ constexpr int N_WS_SLOTS = 12;   // slot 2: the sweep's speculation buffers; 3: 
                                 // 10 / 11: the ELM prediction's scratch / nngp_elm_hidden's partial sums (nngp_elm.hip)
 void *workspace(size_t bytes, int *err, int slot = 0);
 
+// Polynomial vector fields (NNGP_SYS_POLY): the library's registry of term tables
+// (nngp_poly.hip).  One 16-byte record per term: coef and the state indices of its up to three
+// factors in multiplication order, -1 = no factor (only after the real ones).
+struct alignas(16) PolyTerm {
+    double coef;
+    int16_t i, j, k, pad;
+};
+constexpr int POLY_MAX_D = 2048;             // one workgroup per slice, as every field kernel
+constexpr int POLY_MAX_TERMS = 1 << 20;
+constexpr int POLY_LANE_D = 4;               // lane form: d <= 4 and at most 16 terms in total
+constexpr int POLY_LANE_TERMS = 16;
+struct PolyTable {             // a registered table as the host holds it
+    int d, n_terms;
+    const int32_t *row_ptr;    // HOST [d+1]
+    const PolyTerm *terms;     // HOST [n_terms]
+};
+// the table of sys->nx (a handle of nngp_poly_create) after checking it against sys->d: NNGP_E_ARG
+// for an unknown or destroyed handle or another d.  Makes no HIP call.
+int poly_table(const nngp_system *sys, PolyTable *out);
+// the CURRENT device's copy of that table, uploaded on first use and kept until the handle is
+// destroyed or nngp_shutdown (so steady-state calls never allocate)
+int poly_device(const nngp_system *sys, const int32_t **row_ptr, const PolyTerm **terms);
+void poly_release();   // nngp_shutdown's part: every table, host and device
+
 // A prepared coordinate of gp_pre_kernel: alpha rows 0..maxm-1 | c | psy | ok
 __host__ __device__ constexpr int HM_STRIDE(int maxm) { return maxm + 3; }
 

@@ -104,8 +104,12 @@ static void ws_release() {
 // later calls simply re-create what they need.
 extern "C" int nngp_shutdown(void) {
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return NNGP_OK;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
+        nngp::poly_release();   // host tables only: nothing was uploaded
+        return NNGP_OK;
+    }
     (void)hipDeviceSynchronize();
+    nngp::poly_release();
     nngp::chain_release();
     nngp::sweep_release();
     nngp::comm_release();

@@ -89,6 +89,8 @@ __global__ void __launch_bounds__(256) rhs_field_kernel(FieldArgs fa, const doub
             f = burgers_elem(V, e, d, fa);
         } else if constexpr (SYS == NNGP_SYS_DIFFREACT) {
             f = dr_elem(V, e, half, dr_neighbours(fa, e < half ? e : e - half, true), fa);
+        } else if constexpr (SYS == NNGP_SYS_POLY) {
+            f = poly_elem(V, fa.p_row[e], fa.p_row[e + 1], fa.p_terms);
         } else if (e < half) {
             const Nbr5 nb = fhn_neighbours(fa.nx, e);
             const double u1 = V[e];
@@ -173,6 +175,8 @@ extern "C" int nngp_rhs_batch(const nngp_system *sys, int n, const double *u, do
     case NNGP_SYS_BURGERS: return launch_rhs_field<NNGP_SYS_BURGERS>(sys, n, u, out, st);
     case NNGP_SYS_FHN_PDE: return launch_rhs_field<NNGP_SYS_FHN_PDE>(sys, n, u, out, st);
     case NNGP_SYS_DIFFREACT: return launch_rhs_field<NNGP_SYS_DIFFREACT>(sys, n, u, out, st);
+    // one evaluation has no step loop to keep the table in registers for: the field form at every d
+    case NNGP_SYS_POLY: return launch_rhs_field<NNGP_SYS_POLY>(sys, n, u, out, st);
     default: set_error("unknown system kind %d", sys->kind); return NNGP_E_ARG;
     }
 }

@@ -88,14 +88,113 @@ template <> struct LaneSys<NNGP_SYS_DBL_PEND> {  // systems.py:182-189
     }
 };
 
+// ---------------------------------------------------------------------------------------------
+// Polynomial field, lane form (NNGP_SYS_POLY with d <= 4 and at most 16 terms).
+// Every lane evaluates the same table, so the table is wave-uniform: it travels by value in the
+// kernel arguments -- in its own argument type, LaneArgs is what it was -- and lives in scalar
+// registers; the step loop reads no memory.  The 16 terms are unrolled, a term past the table's
+// count leaves the body by one uniform branch, and the factors are picked from the state by a
+// uniform index.  The arithmetic is the contract's: coef times the factors left to right, the
+// row's first term, then acc + term in list order; a row without terms is +0.0.
+// LaneSys<NNGP_SYS_POLY_LANE + D> is the D-component form (D is a compile-time constant so that
+// the state stays in registers and the slice's row stride is the system's d).
+// ---------------------------------------------------------------------------------------------
+struct PolyLaneTab {
+    double coef[POLY_LANE_TERMS];
+    // per term: bits 0-1 the number of factors, 2-3 / 5-6 / 8-9 their indices, 11-12 the row,
+    // 13 first term of its row, 14 last term of its row
+    uint16_t desc[POLY_LANE_TERMS];
+    int n;
+};
+struct PolyLaneArgs : LaneArgs {
+    PolyLaneTab tab;
+};
+constexpr int NNGP_SYS_POLY_LANE = 64;   // + D: not a value of enum nngp_system_kind
+
+// keeps a uniform `if` a scalar branch: without it the compiler turns the skipped work into
+// per-lane selects (two v_cndmask per fp64 value), which cost more than the work they skip
+#define NNGP_POLY_KEEP_BRANCH() asm volatile("")
+
+// eight slots so that x[uniform index] is one indexed register move per half (s_set_gpr_idx) and
+// not a chain of selects over the components (which LLVM makes of up to five fp64 slots); the
+// slots past D are never selected by a table's indices (< D)
+constexpr int POLY_LANE_SLOTS = 8;
+
+// terms T.. of the table, nested: term T + 1 lies inside term T's `if`, so the first term past the
+// table's count leaves all the remaining bodies by ONE taken branch (16 separate `if`s cost a taken
+// branch per missing term; a loop with an early exit is re-rolled by the compiler and then reads
+// the table from the argument segment, memory, inside the step)
+template <int D, int T>
+__device__ __forceinline__ void poly_lane_terms(const PolyLaneTab &tab, int n, const double (&x)[POLY_LANE_SLOTS],
+                                                double (&r)[POLY_LANE_D], double acc) {
+    if constexpr (T < POLY_LANE_TERMS) {
+        if (T < n) {
+            // the descriptor is re-read as a value the compiler cannot trace (also keeps this `if` a
+            // branch): else every field and comparison of all 16 terms is hoisted out of the step
+            // loop into a scalar-register pair each, far more than there are, and comes back into
+            // the loop as v_readlane from spill registers
+            unsigned ds = tab.desc[T];
+            asm volatile("" : "+s"(ds));
+            const unsigned p = ds & 3u;
+            double v = tab.coef[T];
+            if (p >= 1) {
+                NNGP_POLY_KEEP_BRANCH();
+                v = v * x[(ds >> 2) & 3u];
+                if (p >= 2) {
+                    NNGP_POLY_KEEP_BRANCH();
+                    v = v * x[(ds >> 5) & 3u];
+                    if (p >= 3) {
+                        NNGP_POLY_KEEP_BRANCH();
+                        v = v * x[(ds >> 8) & 3u];
+                    }
+                }
+            }
+            // the row's first term: -0.0 + v is v bit for bit (zeros of either sign and NaN included),
+            // so the sum still does not start from 0.0; a select instead of a taken branch
+            const double before = (ds & (1u << 13)) ? -0.0 : acc;
+            acc = before + v;
+            if (__builtin_expect((ds & (1u << 14)) != 0, 0)) {   // the row's last term, out of line
+                NNGP_POLY_KEEP_BRANCH();
+                const unsigned row = (ds >> 11) & 3u;
+#pragma unroll
+                for (int c = 0; c < D; c++)
+                    if (row == (unsigned)c) r[c] = acc;
+            }
+            poly_lane_terms<D, T + 1>(tab, n, x, r, acc);
+        }
+    }
+}
+
+template <int D_> struct PolyLane {
+    static constexpr int D = D_;
+    __device__ __forceinline__ static void f(const double *u, double *o, const PolyLaneArgs &a) {
+        double x[POLY_LANE_SLOTS], r[POLY_LANE_D];
+#pragma unroll
+        for (int c = 0; c < POLY_LANE_SLOTS; c++) x[c] = c < D ? u[c] : 1.0;
+#pragma unroll
+        for (int c = 0; c < POLY_LANE_D; c++) r[c] = 0.0;   // a row without terms: +0.0
+        int n = a.tab.n;
+        asm volatile("" : "+s"(n));   // as the descriptors: compared inside the step, not hoisted
+        poly_lane_terms<D, 0>(a.tab, n, x, r, 0.0);
+#pragma unroll
+        for (int c = 0; c < D; c++) o[c] = r[c];
+    }
+};
+#undef NNGP_POLY_KEEP_BRANCH
+template <> struct LaneSys<NNGP_SYS_POLY_LANE + 1> : PolyLane<1> {};
+template <> struct LaneSys<NNGP_SYS_POLY_LANE + 2> : PolyLane<2> {};
+template <> struct LaneSys<NNGP_SYS_POLY_LANE + 3> : PolyLane<3> {};
+template <> struct LaneSys<NNGP_SYS_POLY_LANE + 4> : PolyLane<4> {};
+
 // f_n(u) = f(inverse(u)) * scale   (systems.py:36-40), inverse(u) = ((u+1)/2)*(mx-mn) + mn
 // (utils.py:24) evaluated as (u+1)*((mx-mn)/2) + mn: halving is exact for normal numbers, so
 // RN(RN(u+1)/2 * w) == RN(RN(u+1) * (w/2)) bit for bit, one multiply fewer per component.  NORM is a template parameter so the RK
 // step loop carries no branches: the lane kernel is VALU-issue-bound (one wave per SIMD, ~4.5
 // cycles per fp64 instruction, dependent or not -- tools/ubench_fp64.hip), so every instruction
 // and every taken scalar branch inside the step is paid in full on the critical path.
-template <int SYS, bool NORM>
-__device__ __forceinline__ void lane_rhs(const double *u, double *o, const LaneArgs &a) {
+// (A: LaneArgs, or the polynomial field's PolyLaneArgs)
+template <int SYS, bool NORM, class A>
+__device__ __forceinline__ void lane_rhs(const double *u, double *o, const A &a) {
     constexpr int D = LaneSys<SYS>::D;
     if constexpr (NORM) {
         double v[D];
@@ -222,7 +321,19 @@ struct FieldArgs {
     int d, nx, normalized;
     const double *norm;   // device [3d] = mn | w | sc, or nullptr
     double c_off, c_diag, c_grad;   // Burgers: nu/dx^2, -2 nu/dx^2, 1/(2dx)
-    double a_off, a_diag, b_off, b_diag;   // FHN-PDE: a*L and b*L entries
+    // FHN-PDE: a*L and b*L entries.  The polynomial field (NNGP_SYS_POLY) keeps the device copy of
+    // its table in the first two's bytes -- no kind uses both -- so the argument block, and with it
+    // every other kernel's code, is what it was.
+    union {
+        struct {
+            double a_off, a_diag;
+        };
+        struct {
+            const int32_t *p_row;     // DEVICE [d+1]
+            const PolyTerm *p_terms;  // DEVICE [n_terms]
+        };
+    };
+    double b_off, b_diag;
     // DiffReact: 1/dx^2, 1/dy^2, the main diagonal -(a)/dx^2 - (b)/dy^2 with a (b) = 2 inside a
     // row (column) and 1 at its two ends (m_ab), and Du, Dv, k
     double r_cx, r_cy, r_m22, r_m12, r_m21, r_m11, r_du, r_dv, r_k;
@@ -284,8 +395,8 @@ struct TrajOut {
 
 // one lane integrates one ODE slice (rk_lane_kernel): u0/uF are the slice's [D] rows; TRAJ: uF is
 // the slice's [n_out][D] block, sampled every `every` steps (TrajOut)
-template <int SYS, int ORDER, bool LINSPACE, bool NORM, bool TRAJ = false>
-__device__ __forceinline__ void lane_slice(LaneArgs args, double T0, double T1, int64_t steps, int64_t gsteps,
+template <int SYS, int ORDER, bool LINSPACE, bool NORM, bool TRAJ = false, class A = LaneArgs>
+__device__ __forceinline__ void lane_slice(A args, double T0, double T1, int64_t steps, int64_t gsteps,
                                            int64_t j0, const double *__restrict__ u0, double *__restrict__ uF,
                                            int64_t every = 0) {
     using T = Tableau<ORDER>;

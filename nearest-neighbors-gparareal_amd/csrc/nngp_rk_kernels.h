@@ -35,6 +35,28 @@ __global__ void __launch_bounds__(64) rk_lane_kernel(LaneArgs args, int n_slices
                                                u0 + (size_t)i * D, uF + (size_t)i * D);
 }
 
+// The lane kernel of the polynomial field (d = D <= 4, at most 16 terms): rk_lane_kernel's body --
+// the same lane_slice -- on LaneSys<NNGP_SYS_POLY_LANE + D>, with the table in its own argument
+// type (PolyLaneArgs), so rk_lane_kernel's argument block and symbols stay what they were.  There is
+// no group form of it.
+template <int D, int ORDER, bool LINSPACE, bool NORM, bool TRAJ>
+__global__ void __launch_bounds__(64) rk_poly_lane_kernel(PolyLaneArgs args, int n_slices,
+                                                          const double *__restrict__ t0,
+                                                          const double *__restrict__ t1, int64_t steps,
+                                                          int64_t gsteps, const int64_t *__restrict__ j0s,
+                                                          const double *__restrict__ u0,
+                                                          double *__restrict__ uF) {
+    constexpr int SYS = NNGP_SYS_POLY_LANE + D;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_slices) return;
+    if constexpr (TRAJ)
+        lane_slice<SYS, ORDER, LINSPACE, NORM, true>(args, t0[i], t1[i], steps, steps, 0, u0 + (size_t)i * D,
+                                                     traj_block(uF, i, steps, gsteps, D), gsteps);
+    else
+        lane_slice<SYS, ORDER, LINSPACE, NORM>(args, t0[i], t1[i], steps, gsteps, j0s ? j0s[i] : 0,
+                                               u0 + (size_t)i * D, uF + (size_t)i * D);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Lane-group kernel: one slice = one group of G lanes, each component on its own lanes: G = 16
 // (components in DPP banks, below) for every ODE but Thomas labyrinth, G = 4 (lane c = component c,
@@ -656,6 +678,25 @@ __device__ __forceinline__ double dr_elem(const double *__restrict__ V, int e, i
     return isv ? dr_fv(V[p], V[e], lap, fa) : dr_fu(V[e], V[half + e], lap, fa);
 }
 
+// Polynomial field (NNGP_SYS_POLY): row e of the table from the image V, its terms
+// b .. en-1 walked in list order from device memory -- one 16-byte record, one global_load_dwordx4,
+// per term (wave-divergent where the rows of a wave differ in length; the table of every slice is
+// the same, so it stays in cache).  coef times the factors left to right, the first term, then
+// acc + term; no terms: +0.0.  The indices were checked when the table was registered.
+__device__ __forceinline__ double poly_elem(const double *__restrict__ V, int b, int en,
+                                            const PolyTerm *__restrict__ terms) {
+    double acc = 0.0;
+    for (int t = b; t < en; t++) {
+        const PolyTerm T = terms[t];
+        double v = T.coef;
+        if (T.i >= 0) v = v * V[T.i];
+        if (T.j >= 0) v = v * V[T.j];
+        if (T.k >= 0) v = v * V[T.k];
+        acc = (t == b) ? v : acc + v;
+    }
+    return acc;
+}
+
 // <= 256 threads per slice leaves ~170 VGPRs for u, the S stage vectors and the neighbour table
 template <int SYS, int ORDER, bool LINSPACE, int EPT, bool NORM, bool TRAJ>
 __global__ void __launch_bounds__(EPT == 1 ? 1024 : (EPT == 2 ? 512 : 256)) rk_field_kernel(FieldArgs fa, int n_slices,
@@ -678,11 +719,16 @@ __global__ void __launch_bounds__(EPT == 1 ? 1024 : (EPT == 2 ? 512 : 256)) rk_f
     int e_[EPT];
     Nbr5 nb[(SYS == NNGP_SYS_FHN_PDE) ? EPT : 1];
     DrNbr rnb[(SYS == NNGP_SYS_DIFFREACT) ? EPT : 1];
+    int pb[(SYS == NNGP_SYS_POLY) ? EPT : 1], pe[(SYS == NNGP_SYS_POLY) ? EPT : 1];   // the rows' term ranges
 #pragma unroll
     for (int r = 0; r < EPT; r++) {
         const int e = tid + r * BT;
         e_[r] = e;
         const bool ok = e < d;
+        if constexpr (SYS == NNGP_SYS_POLY) {
+            pb[r] = ok ? fa.p_row[e] : 0;
+            pe[r] = ok ? fa.p_row[e + 1] : 0;
+        }
         u[r] = ok ? u0[(size_t)slice * d + e] : 0.0;
         if (NORM && ok) {
             mn[r] = fa.norm[e];
@@ -734,6 +780,8 @@ __global__ void __launch_bounds__(EPT == 1 ? 1024 : (EPT == 2 ? 512 : 256)) rk_f
                         f = burgers_elem(V, e, d, fa);
                     } else if constexpr (SYS == NNGP_SYS_DIFFREACT) {
                         f = dr_elem(V, e, half, rnb[r], fa);
+                    } else if constexpr (SYS == NNGP_SYS_POLY) {
+                        f = poly_elem(V, pb[r], pe[r], fa.p_terms);
                     } else {   // FHN_PDE, systems.py:365-366
                         if (e < half) {
                             const double lu = fhn_lap(V, nb[r], fa.a_off, fa.a_diag);
@@ -1194,6 +1242,11 @@ static int field_args(const nngp_system *sys, FieldArgs &fa) {
         fa.r_du = sys->param[0];
         fa.r_dv = sys->param[1];
         fa.r_k = sys->param[2];
+    } else if (sys->kind == NNGP_SYS_POLY) {
+        // the handle and d are checked on the host first; only then the device copy (uploaded on
+        // this device's first use)
+        int rc = poly_device(sys, &fa.p_row, &fa.p_terms);
+        if (rc) return rc;
     } else {
         NNGP_REQUIRE(sys->nx >= 3 && sys->d == 2 * sys->nx * sys->nx, "FHN_PDE needs d = 2 nx^2, nx >= 3");
         const double dx = (1.0 - (-1.0)) / (sys->nx - 1);
@@ -1283,6 +1336,59 @@ static int launch_field(const nngp_system *sys, int n, const double *t0, const d
     return launch_field_ept<SYS, ORDER, LIN, 8, TRAJ>(fa, bt, n, t0, t1, steps, gsteps, j0, u0, uF, st);
 }
 
+// the lane form's descriptor of one term (PolyLaneTab, nngp_rk_dev.h)
+static void poly_lane_tab(const PolyTable &pt, PolyLaneTab &tab) {
+    tab = PolyLaneTab{};
+    tab.n = pt.n_terms;
+    for (int c = 0; c < pt.d; c++)
+        for (int t = pt.row_ptr[c]; t < pt.row_ptr[c + 1]; t++) {
+            const PolyTerm &T = pt.terms[t];
+            const unsigned p = (T.i >= 0) + (T.j >= 0) + (T.k >= 0);
+            tab.coef[t] = T.coef;
+            tab.desc[t] = (uint16_t)(p | (unsigned)(T.i >= 0 ? T.i : 0) << 2 | (unsigned)(T.j >= 0 ? T.j : 0) << 5 |
+                                     (unsigned)(T.k >= 0 ? T.k : 0) << 8 | (unsigned)c << 11 |
+                                     (unsigned)(t == pt.row_ptr[c]) << 13 | (unsigned)(t + 1 == pt.row_ptr[c + 1]) << 14);
+        }
+}
+
+template <int D, int ORDER, bool LIN, bool TRAJ>
+static int launch_poly_lane(const nngp_system *sys, const PolyTable &pt, int n, const double *t0, const double *t1,
+                            int64_t steps, int64_t gsteps, const int64_t *j0, const double *u0, double *uF,
+                            hipStream_t st) {
+    PolyLaneArgs a{};
+    a.normalized = sys->normalized;
+    a.norm = sys->norm;
+    poly_lane_tab(pt, a.tab);
+    const int bs = 64;
+    if (sys->normalized)
+        hipLaunchKernelGGL((rk_poly_lane_kernel<D, ORDER, LIN, true, TRAJ>), dim3((n + bs - 1) / bs), dim3(bs), 0, st,
+                           a, n, t0, t1, steps, gsteps, j0, u0, uF);
+    else
+        hipLaunchKernelGGL((rk_poly_lane_kernel<D, ORDER, LIN, false, TRAJ>), dim3((n + bs - 1) / bs), dim3(bs), 0, st,
+                           a, n, t0, t1, steps, gsteps, j0, u0, uF);
+    NNGP_LAUNCH_CHECK();
+    return NNGP_OK;
+}
+
+// NNGP_SYS_POLY: the lane form while the table fits the kernel arguments (d <= 4 and at most 16
+// terms), else the field form (one workgroup per slice, the table in device memory)
+template <int ORDER, bool LIN, bool TRAJ>
+static int launch_poly(const nngp_system *sys, int n, const double *t0, const double *t1, int64_t steps,
+                       int64_t gsteps, const int64_t *j0, const double *u0, double *uF, hipStream_t st) {
+    PolyTable pt;
+    int rc = poly_table(sys, &pt);   // host checks, before any HIP call
+    if (rc) return rc;
+    NNGP_REQUIRE(!sys->normalized || sys->norm != nullptr, "normalized system needs norm[3d]");
+    if (pt.d > POLY_LANE_D || pt.n_terms > POLY_LANE_TERMS)
+        return launch_field<NNGP_SYS_POLY, ORDER, LIN, TRAJ>(sys, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    switch (pt.d) {
+    case 1: return launch_poly_lane<1, ORDER, LIN, TRAJ>(sys, pt, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    case 2: return launch_poly_lane<2, ORDER, LIN, TRAJ>(sys, pt, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    case 3: return launch_poly_lane<3, ORDER, LIN, TRAJ>(sys, pt, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    default: return launch_poly_lane<4, ORDER, LIN, TRAJ>(sys, pt, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    }
+}
+
 template <int ORDER, bool LIN, bool TRAJ>
 static int dispatch_sys(const nngp_system *s, int n, const double *t0, const double *t1,
                         int64_t steps, int64_t gsteps, const int64_t *j0, const double *u0,
@@ -1301,6 +1407,7 @@ static int dispatch_sys(const nngp_system *s, int n, const double *t0, const dou
     case NNGP_SYS_FHN_PDE: return launch_field<NNGP_SYS_FHN_PDE, ORDER, LIN, TRAJ>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
     case NNGP_SYS_DIFFREACT:
         return launch_field<NNGP_SYS_DIFFREACT, ORDER, LIN, TRAJ>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    case NNGP_SYS_POLY: return launch_poly<ORDER, LIN, TRAJ>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
     default: set_error("unknown system kind %d", s->kind); return NNGP_E_ARG;
     }
 }

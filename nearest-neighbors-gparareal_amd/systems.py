@@ -193,3 +193,76 @@ class DiffReact(ODE):
         mn, mx = np.array([[-4] * d, [4] * d])
         u0 = np.random.default_rng(seed).uniform(size=d)
         super().__init__(f'DiffReact2D_{d_x}', mn, mx, u0, param=(float(Du), float(Dv), float(k)), **kwargs)
+
+
+class PolyODE(ODE):
+    """A user-defined polynomial system: the counterpart of subclassing the reference's ODE and
+    writing _f_np / _f_jax (systems.py:23-61), with the right-hand side given as data.
+
+    terms[c] is the ordered list of row c's terms (coef, indices), 0 to 3 indices in [0, d) each:
+        du_c/dt = sum over the list of  coef * u[i1] * u[i2] * u[i3]
+    evaluated exactly as written -- coef times the factors left to right, the first term plus the
+    following ones in list order, an empty list giving 0.0.  Brusselator is
+        PolyODE([[(1, ()), (1, (0, 0, 1)), (-4, (0,))], [(3, (0,)), (-1, (0, 0, 1))]], u0=[1, 3.07])
+    normalization='-11' needs mn and mx.  The library's table (nngp_poly_create) is made on the
+    first use of the descriptor and destroyed with the object; everything else is ODE's, so
+    SolverRK, Parareal, build_cont_traj and the legacy solver take it like any other system."""
+    kind = _lib.SYS_POLY
+    MAX_D, MAX_DEGREE = 2048, 3
+
+    def __init__(self, terms, u0, mn=None, mx=None, name='PolyODE', normalization=None, **kwargs):
+        u0 = np.array(u0, dtype=float)
+        if u0.ndim != 1 or not 1 <= u0.shape[0] <= self.MAX_D:
+            raise ValueError(f'PolyODE: u0 must be a vector of 1..{self.MAX_D} components')
+        d = u0.shape[0]
+        if len(terms) != d:
+            raise ValueError(f'PolyODE: {len(terms)} rows of terms for d = {d}')
+        if normalization is not None and normalization.lower() == '-11':
+            if mn is None or mx is None:
+                raise ValueError("PolyODE: normalization='-11' needs mn and mx")
+            mn = np.broadcast_to(np.asarray(mn, dtype=float), (d,)).copy()
+            mx = np.broadcast_to(np.asarray(mx, dtype=float), (d,)).copy()
+        row_ptr, coef, idx = [0], [], []
+        for c, row in enumerate(terms):
+            for coef_t, ind in row:
+                ind = [int(i) for i in ind]
+                if len(ind) > self.MAX_DEGREE:
+                    raise ValueError(f'PolyODE: row {c} has a term of degree {len(ind)} (at most {self.MAX_DEGREE})')
+                if any(not 0 <= i < d for i in ind):
+                    raise ValueError(f'PolyODE: row {c} has an index outside [0, {d})')
+                if not np.isfinite(coef_t):
+                    raise ValueError(f'PolyODE: row {c} has a coefficient that is not finite')
+                coef.append(float(coef_t))
+                idx.append(ind + [-1] * (self.MAX_DEGREE - len(ind)))
+            row_ptr.append(len(coef))
+        self.terms = [[(float(a), tuple(int(i) for i in ind)) for a, ind in row] for row in terms]
+        self._row_ptr = np.array(row_ptr, dtype=np.int32)
+        self._coef = np.array(coef, dtype=np.float64)
+        self._idx = np.array(idx, dtype=np.int16).reshape(-1, 3)
+        self._handle = None
+        super().__init__(name, mn, mx, u0, normalization=normalization, **kwargs)
+
+    @property
+    def nx(self):
+        """nngp_system.nx of this kind: the table's handle, created on first use"""
+        if self._handle is None:
+            h = ctypes.c_int32(0)
+            _lib.check(_lib.lib().nngp_poly_create(
+                self.d, len(self._coef), self._row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                self._coef.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                self._idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), ctypes.byref(h)))
+            self._handle = int(h.value)
+        return self._handle
+
+    def destroy(self):
+        """Free the library's table now (else when the object goes); descriptors made from it are
+        refused from then on."""
+        h, self._handle = getattr(self, '_handle', None), None
+        if h is not None and _lib._lib is not None:
+            _lib._lib.nngp_poly_destroy(h)   # after nngp_shutdown the table is gone already: ignored
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:   # interpreter teardown
+            pass
