@@ -133,6 +133,33 @@ int nngp_rk_traj(const nngp_system *sys, int tableau, int step_mode, int n_slice
                  const double *t0, const double *t1, int64_t steps, int64_t every,
                  const double *u0, double *traj, void *stream);
 
+/* Adaptive fine propagator (replaces SolverScipy.run_F -> scipy.integrate.solve_ivp(f, [t0, t1],
+ * u0, method, t_eval=(t1,), max_step=(t1-t0)/Nf, **kwargs), solver.py:138-145, for every slice of
+ * one Parareal iteration).  Slice i integrates u0[i] from t0[i] to t1[i] (forward only) with the
+ * embedded pair `method` under scipy's step-size control -- rtol, atol scalars, max_step =
+ * (t1[i]-t0[i])/nf, first_step = 0 to select the initial step as scipy does (a first_step beyond
+ * a slice's length is the caller's to refuse, as validate_first_step does; here it is clipped to
+ * max_step) -- and writes y_new of its last accepted step to uF[i].  The arithmetic is a fully
+ * specified operation order (tests/adaptive_ref.py), not scipy's BLAS / libm one:
+ * step counts equal scipy's on the recorded cases and end states agree to ~1e-13 relative.
+ * A slice stops after max_attempts attempted steps, whatever its arithmetic does.
+ * stats: DEVICE int64 [n_slices][4] = status, nfev, accepted steps, rejected steps, or NULL;
+ *   status 0 = reached t1, 1 = step size below min_step = 10*|nextafter(t, inf) - t|,
+ *   2 = max_attempts reached.  On a non-zero status uF[i] is the last accepted state.  A slice
+ *   with t1 <= t0 takes no step (uF[i] = u0[i], status 0).
+ * Stream-ordered, no host synchronisation; uF may alias u0; n_slices = 0 is a no-op.  Exact build
+ * only: there is no NNGP_STEP_CONTRACT form.  Field systems take d <= 2048.
+ * NNGP_E_ARG before any HIP call: unknown method; nf < 1; rtol <= 0, atol < 0 or a non-finite
+ * tolerance; first_step < 0; max_attempts < 1; an unknown or destroyed NNGP_SYS_POLY handle.
+ * t0, t1: DEVICE [n_slices]; u0, uF: DEVICE [n_slices][sys->d].                              */
+enum nngp_adaptive_method { NNGP_RK23 = 23, NNGP_RK45 = 45 };
+int nngp_rk_adaptive(const nngp_system *sys, int method, int n_slices,
+                     const double *t0, const double *t1, int64_t nf,   /* max_step = (t1-t0)/nf */
+                     double rtol, double atol, double first_step,      /* 0 = choose */
+                     int64_t max_attempts, const double *u0, double *uF,
+                     int64_t *stats /* DEVICE [n][4] = status, nfev, accepted, rejected; or NULL */,
+                     void *stream);
+
 /* Vector field evaluation f_n(u) for n states (what ODE.get_vector_field() returns as a
  * callable, systems.py:32-44).  u, out: DEVICE [n][sys->d].                                 */
 int nngp_rhs_batch(const nngp_system *sys, int n, const double *u, double *out, void *stream);

@@ -19,10 +19,11 @@ SYS_LORENZ, SYS_HOPF, SYS_THOMAS_LABYRINTH, SYS_FHN_ODE, SYS_ROSSLER = 0, 1, 2, 
 SYS_BRUSSELATOR, SYS_DBL_PEND, SYS_BURGERS, SYS_FHN_PDE, SYS_DIFFREACT = 5, 6, 7, 8, 9
 SYS_POLY = 10
 TABLEAU = {'RK1': 1, 'RK2': 2, 'RK4': 4, 'RK8': 8}
+ADAPTIVE = {'RK23': 23, 'RK45': 45}   # enum nngp_adaptive_method
 STEP_FIXED, STEP_LINSPACE, STEP_CONTRACT = 0, 1, 16
 
 EXPORTS = ['nngp_abi_version', 'nngp_last_error', 'nngp_device_count', 'nngp_rk_batch', 'nngp_rk_batch_grid',
-           'nngp_rk_traj',
+           'nngp_rk_traj', 'nngp_rk_adaptive',
            'nngp_rhs_batch', 'nngp_parareal_update', 'nngp_knn', 'nngp_nm_fit_batch',
            'nngp_gp_mean', 'nngp_predict', 'nngp_correction_sweep', 'nngp_gpfull_lml', 'nngp_gpfull_fit',
            'nngp_gpfull_mean', 'nngp_predict_range', 'nngp_chain_stats', 'nngp_sweep_late_reruns', 'nngp_shutdown',
@@ -70,6 +71,8 @@ def lib():
     L.nngp_rk_batch.argtypes = [ctypes.POINTER(CSystem), i32, i32, i32, _vp, _vp, i64, _vp, _vp, _vp]
     L.nngp_rk_batch_grid.argtypes = [ctypes.POINTER(CSystem), i32, i32, _vp, _vp, i64, _vp, i64, _vp, _vp, _vp]
     L.nngp_rk_traj.argtypes = [ctypes.POINTER(CSystem), i32, i32, i32, _vp, _vp, i64, i64, _vp, _vp, _vp]
+    L.nngp_rk_adaptive.argtypes = [ctypes.POINTER(CSystem), i32, i32, _vp, _vp, i64, dbl, dbl, dbl, i64, _vp, _vp,
+                                   _vp, _vp]
     L.nngp_rhs_batch.argtypes = [ctypes.POINTER(CSystem), i32, _vp, _vp, _vp]
     L.nngp_parareal_update.argtypes = [i64, _vp, _vp, _vp, _vp, _vp]
     L.nngp_knn.argtypes = [_vp, i64, i32, _vp, i32, _vp, _vp, _vp]

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from .parareal import Parareal as _Parareal
-from .solver import SolverRK
+from .solver import SolverRK, SolverScipy
 from .systems import FHN_ODE, DblPend, Hopf, Lorenz, Rossler
 
 
@@ -103,6 +103,10 @@ class Parareal(_Parareal):
             self.data_tr = self.data_tr_inv = lambda x: x
         if not hasattr(f, 'csystem'):
             raise TypeError('f must be the VectorField of an nngp_amd ODE (ode.get_vector_field())')
+        # new_lib has fixed-step propagators only (new_lib.py:57-137)
+        if isinstance(kwargs.get('solver'), SolverScipy) or F in ('RK23', 'RK45', 'DOP853'):
+            raise NotImplementedError('the legacy driver has no adaptive fine solver (SolverScipy): use '
+                                      'nngp_amd.Parareal with nngp_amd.SolverScipy')
         self.RK_thresh = RK_thresh
         self.Ng, self.Nf, self.F, self.G = int(Ng), int(Nf), F, G
         solver = LegacySolverRK(f, N, Ng, Nf, F, G, RK_thresh)

@@ -16,6 +16,10 @@ Step conventions (include/nngp.h):
 `fma=True` (opt-in; env NNGP_RK_CONTRACT=1 flips the default) runs F and G on the contracted code
 object (NNGP_STEP_CONTRACT): a*b+c fused, ~25 % fewer fp64 instructions per step, end states within
 1e-12 relative of the exact build instead of bitwise (tests/test_gpu_contract.py).
+
+`SolverScipy` (solver.py:116-148) is the adaptive fine propagator: scipy's RK23 / RK45 step-size
+control with max_step = (t1-t0)/Nf, every slice in one launch (nngp_rk_adaptive), G through the
+fixed-step SolverRK it derives from.
 """
 import os
 import ctypes
@@ -236,3 +240,122 @@ class SolverRK(SolverAbstr):
 
     def run_G_full(self, t0, t1, u0, every=1):
         return self._full(self.G, self.Ng, t0, t1, u0, every)
+
+
+class SolverScipy(SolverRK):
+    """The reference's adaptive fine propagator (solver.py:116-148): F is scipy's RK23 or RK45 with
+    max_step = (t1-t0)/Nf per slice, every slice of an iteration in ONE launch (nngp_rk_adaptive);
+    G is the fixed-step SolverRK it is derived from, as the reference's inner `rk_solver`.
+
+    F: 'RK45' / 'RK4', 'RK23' / 'RK2' (solver.py:130-135).  kwargs are those the reference forwards
+    to solve_ivp: rtol (1e-3), atol (1e-6), both scalars, and first_step (None: selected as scipy
+    does); plus max_attempts, the cap on attempted steps per slice (100*Nf + 1000).  The arithmetic
+    is the fixed operation order of DESIGN.md 3.2d (tests/adaptive_ref.py), not scipy's BLAS and
+    libm one; only the exact build is offered (no fma).  After every launch `last_stats` holds the
+    per-slice 'status', 'nfev', 'n_accepted' and 'n_rejected' as numpy arrays (the reference's
+    "did x more steps" print fires on every RK45 call by construction and is dropped).
+    """
+
+    _MAP = {'RK2': 'RK23', 'RK4': 'RK45', 'RK8': 'DOP853'}   # solver.py:131
+    _WHY = {1: 'the required step size fell below the spacing between numbers (min_step)',
+            2: 'max_attempts attempted steps were reached'}
+
+    def __init__(self, f, Ng, Nf, G, F='RK45', use_jax=True, **kwargs):
+        kwargs = dict(kwargs)
+        if kwargs.pop('fma', None) or os.environ.get('NNGP_RK_CONTRACT') == '1':
+            raise NotImplementedError('SolverScipy has no contracted build: fma=True / NNGP_RK_CONTRACT=1 is not '
+                                      'offered with the adaptive propagator')
+        method = self._map_solver(F)
+        if method not in _lib.ADAPTIVE:
+            raise NotImplementedError(f'SolverScipy: method {method!r} is not implemented (only RK23 and RK45)')
+        rtol = kwargs.pop('rtol', 1e-3)
+        atol = kwargs.pop('atol', 1e-6)
+        first_step = kwargs.pop('first_step', None)
+        max_attempts = kwargs.pop('max_attempts', None)
+        if kwargs:
+            raise TypeError(f'SolverScipy: keyword {sorted(kwargs)[0]!r} is not supported (rtol, atol, first_step, '
+                            'max_attempts)')
+        for name, v in (('rtol', rtol), ('atol', atol)):
+            if np.ndim(v) != 0:
+                raise TypeError(f'SolverScipy: {name} must be a scalar (an array {name} is not supported)')
+        rtol, atol = float(rtol), float(atol)
+        if not (np.isfinite(rtol) and rtol > 0):
+            raise ValueError(f'SolverScipy: rtol must be positive and finite (got {rtol})')
+        if not (np.isfinite(atol) and atol >= 0):
+            raise ValueError(f'SolverScipy: atol must be non-negative and finite (got {atol})')
+        eps100 = 100 * np.finfo(float).eps
+        if rtol < eps100:   # scipy's validate_tol
+            import warnings
+            warnings.warn(f'At least one element of `rtol` is too small. Setting `rtol = np.maximum(rtol, {eps100})`.',
+                          stacklevel=2)
+            rtol = eps100
+        if first_step is not None:
+            if np.ndim(first_step) != 0:
+                raise TypeError('SolverScipy: first_step must be a scalar')
+            first_step = float(first_step)
+            if not (np.isfinite(first_step) and first_step > 0):   # validate_first_step
+                raise ValueError('SolverScipy: `first_step` must be positive.')
+        super().__init__(f, Ng, Nf, F=G, G=G, fma=False)
+        self.F = method
+        if max_attempts is None:
+            max_attempts = 100 * self.Nf + 1000
+        if int(max_attempts) != max_attempts or int(max_attempts) < 1:
+            raise ValueError(f'SolverScipy: max_attempts must be an integer >= 1 (got {max_attempts})')
+        self.rtol, self.atol, self.first_step, self.max_attempts = rtol, atol, first_step, int(max_attempts)
+        self.kwargs = dict(rtol=rtol, atol=atol, first_step=first_step)
+        self.last_stats = None
+
+    def _map_solver(self, solver):
+        return self._MAP.get(solver, solver)
+
+    def run_F_batch(self, t0, t1, U0, out=None, stream=None):
+        """Integrate U0[i] from t0[i] to t1[i] for all i in one launch, then read the per-slice
+        status back (one small device-to-host copy) and raise NNGPError for the first slice that
+        did not reach t1."""
+        import torch
+        if out is None:
+            out = torch.empty_like(U0)
+        n = U0.shape[0]
+        if n == 0:
+            z = np.zeros(0, dtype=np.int64)
+            self.last_stats = dict(status=z, nfev=z.copy(), n_accepted=z.copy(), n_rejected=z.copy())
+            return out
+        assert U0.dtype == torch.float64 and U0.is_contiguous() and U0.is_cuda
+        if not torch.is_tensor(t0):
+            t0 = torch.tensor(np.asarray(t0, dtype=float), device=U0.device)
+            t1 = torch.tensor(np.asarray(t1, dtype=float), device=U0.device)
+        if self.first_step is not None and self.first_step > float((t1 - t0).abs().min()):   # validate_first_step
+            raise ValueError('SolverScipy: `first_step` exceeds bounds.')
+        cs = self.f.csystem(U0.device)
+        stats = torch.empty((n, 4), dtype=torch.int64, device=U0.device)
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().nngp_rk_adaptive(ctypes.byref(cs), _lib.ADAPTIVE[self.F], n, t0.data_ptr(), t1.data_ptr(),
+                                               self.Nf, self.rtol, self.atol, self.first_step or 0.0,
+                                               self.max_attempts, U0.data_ptr(), out.data_ptr(), stats.data_ptr(), st))
+        if stream is not None:   # the copy below must follow the launch on the caller's stream
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream)):
+                h = stats.cpu().numpy()
+        else:
+            h = stats.cpu().numpy()
+        self.last_stats = dict(status=h[:, 0].copy(), nfev=h[:, 1].copy(), n_accepted=h[:, 2].copy(),
+                               n_rejected=h[:, 3].copy())
+        bad = np.flatnonzero(h[:, 0])
+        if bad.size:
+            i = int(bad[0])
+            raise _lib.NNGPError(f'SolverScipy ({self.F}): slice {i} of {n} failed with status {int(h[i, 0])}: '
+                                 f'{self._WHY.get(int(h[i, 0]), "unknown status")} after {int(h[i, 2])} accepted and '
+                                 f'{int(h[i, 3])} rejected steps ({bad.size} failing slice(s) in this launch)')
+        return out
+
+    def run_F(self, t0, t1, u0):
+        torch = _lib.require_gpu()
+        U0 = torch.tensor(np.asarray(u0, dtype=np.float64).reshape(1, -1), device='cuda')
+        return self.run_F_batch(np.array([t0], dtype=float), np.array([t1], dtype=float), U0)[0].cpu().numpy()
+
+    # the reference's SolverScipy has no run_F_full either (solver.py:116-148)
+    def run_F_traj_batch(self, *args, **kwargs):
+        raise NotImplementedError('SolverScipy has no sampled fine trajectory (run_F_traj_batch, run_F_full, '
+                                  'Parareal.build_cont_traj): the adaptive propagator has no dense output')
+
+    def run_F_full(self, t0, t1, u0, every=1):
+        return self.run_F_traj_batch()
