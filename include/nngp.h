@@ -433,6 +433,34 @@ int nngp_elm_sweep(const nngp_system *sys, int g_tableau, int g_step_mode, int64
                    const double *Y, const double *H, int64_t rows, int m, int degree, int res_size,
                    const double *bias_h, const double *C, float *g_ms_out, void *stream);
 
+/* ---- 7. k-NN Parareal correction (Figure_2.py:455-475, NN.predict) ------------------------
+ * The plain average of the m nearest neighbours' targets (restated in
+ * tests/knnmean_ref.py): the neighbours i_0 .. i_{m-1} are nngp_knn's ordered list; per coordinate
+ * s = Y[i_0][c], s = s + Y[i_r][c] for r = 1 .. m-1 in that order, mean = s / (double)m.
+ *
+ * nngp_knn_mean: the means of the m_j nearest rows for every query and every count, as one
+ * distance launch and one select-and-mean launch on `stream`, with no host synchronisation.  The
+ * neighbours are selected once at max(m_j); the mean for m_j is the running sum after m_j rows
+ * over m_j, bitwise what a call with that count alone gives, and a query's bits do not depend on
+ * the queries it is batched with.
+ *   X, Y DEVICE [rows][d];  Q DEVICE [n_q][d], 0 <= n_q <= 65535 (0 is a no-op);
+ *   m_host HOST [n_m], 1 <= n_m <= 16, each 1 <= m_j <= min(64, rows), any order, repeats allowed;
+ *   out DEVICE [n_m][n_q][d];  idx_out DEVICE int32 [n_q][max m_j] or NULL;
+ *   bias / out_biased DEVICE [d], both or neither, n_q == n_m == 1 only: out_biased = out + bias. */
+int nngp_knn_mean(const double *X, const double *Y, int64_t rows, int d, const double *Q, int n_q,
+                  const int32_t *m_host, int n_m, double *out, int32_t *idx_out, const double *bias,
+                  double *out_biased, void *stream);
+
+/* nngp_knn_mean_sweep: the sequential sweep of one iteration with the k-NN model, shaped like
+ * nngp_elm_sweep: for i = I .. N-1
+ *     UG1[i+1] = G(t[i], t[i+1], U1[i])             (nngp_rk_batch)
+ *     U1[i+1]  = mean + UG1[i+1],  preds[i-I] = mean  (preds DEVICE [N-I][d] or NULL)
+ * two launches per slice, all on `stream`.  N <= I is a no-op.  g_ms_out as in nngp_elm_sweep.   */
+int nngp_knn_mean_sweep(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t g_steps,
+                        const double *t, int I, int N, double *U1, double *UG1, const double *X,
+                        const double *Y, int64_t rows, int m, double *preds, float *g_ms_out,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

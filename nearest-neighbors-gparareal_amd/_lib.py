@@ -29,7 +29,8 @@ EXPORTS = ['nngp_abi_version', 'nngp_last_error', 'nngp_device_count', 'nngp_rk_
            'nngp_gpfull_mean', 'nngp_predict_range', 'nngp_chain_stats', 'nngp_sweep_late_reruns', 'nngp_shutdown',
            'nngp_comm_available', 'nngp_comm_unique_id', 'nngp_comm_init', 'nngp_comm_size', 'nngp_comm_destroy',
            'nngp_allgather_states', 'nngp_correction_sweep_sharded', 'nngp_correction_sweep_sharded_emulated',
-           'nngp_elm_hidden', 'nngp_elm_predict', 'nngp_elm_sweep', 'nngp_poly_create', 'nngp_poly_destroy']
+           'nngp_elm_hidden', 'nngp_elm_predict', 'nngp_elm_sweep', 'nngp_poly_create', 'nngp_poly_destroy',
+           'nngp_knn_mean', 'nngp_knn_mean_sweep']
 MODEL_PARAREAL, MODEL_NNGP, MODEL_GPFULL = 0, 1, 2
 
 
@@ -111,6 +112,9 @@ def lib():
                                  i32, i32, i32, _vp, _vp, ctypes.POINTER(ctypes.c_float), _vp]
     L.nngp_poly_create.argtypes = [i32, i32, _ip, _dp, ctypes.POINTER(ctypes.c_int16), _ip]
     L.nngp_poly_destroy.argtypes = [ctypes.c_int32]
+    L.nngp_knn_mean.argtypes = [_vp, _vp, i64, i32, _vp, i32, _ip, i32, _vp, _vp, _vp, _vp, _vp]
+    L.nngp_knn_mean_sweep.argtypes = [ctypes.POINTER(CSystem), i32, i32, i64, _vp, i32, i32, _vp, _vp, _vp, _vp, i64,
+                                      i32, _vp, ctypes.POINTER(ctypes.c_float), _vp]
     for name in EXPORTS:
         if name not in ('nngp_abi_version', 'nngp_last_error', 'nngp_device_count', 'nngp_chain_stats',
                         'nngp_sweep_late_reruns'):

@@ -136,8 +136,10 @@ class Parareal(_Parareal):
         # runs (new_lib.py:902-997), and the scalability scripts re-assign them after construction
         # (Hopf.py:68-69: s.Nf = s.Nf * 10000; s.RK_thresh = s.Nf/s.N/scaling)
         model = args[0] if args else kwargs.get('model', 'parareal')
-        if isinstance(model, str) and model.lower() == 'elm':   # new_lib's driver has no ELM branch
+        if isinstance(model, str) and model.lower() in ('elm', 'nn'):   # new_lib's driver has no ELM / k-NN branch
             raise Exception('Not implemented')
+        if kwargs.get('comp_mdls') is not None:   # nor Figure_2.py's comparison loop
+            raise NotImplementedError('the legacy driver has no model comparison (comp_mdls): use nngp_amd.Parareal')
         self._setup_solver()
         return super().run(*args, **kwargs)
 

@@ -820,3 +820,148 @@ class ELM(ModelAbstr):
         st = super().state_dict()
         st['settings'] = dict(self.settings)
         return st
+
+
+# ------------------------------------------------------------------------------------------ k-NN
+KNN_MAX_COUNTS = 16   # counts one nngp_knn_mean launch serves (include/nngp.h)
+
+
+def _nn_count(nn):
+    """The neighbour count of the k-NN model: an integer in 1..MAX_NEIGHBOURS."""
+    if isinstance(nn, str) or isinstance(nn, bool) or not isinstance(nn, (int, np.integer)):
+        raise ValueError(f"nn={nn!r}: the k-NN correction takes an integer neighbour count "
+                         f"(1..{MAX_NEIGHBOURS}); 'adaptive' is a mode of NNGP_p only")
+    if nn < 1:
+        raise ValueError(f'nn={nn}: the k-NN correction needs nn >= 1')
+    if nn > MAX_NEIGHBOURS:
+        raise ValueError(f'nn={nn}: the GPU k-NN correction supports at most {MAX_NEIGHBOURS} neighbours')
+    return int(nn)
+
+
+def _knn_tensor(t, name, shape, device, dtype=None):
+    """A device tensor handed to nngp_knn_mean by address: it must be what the kernel reads it as."""
+    import torch
+    dtype = torch.float64 if dtype is None else dtype
+    if not torch.is_tensor(t) or t.dtype != dtype or t.device != device or tuple(t.shape) != tuple(shape) \
+            or not t.is_contiguous():
+        what = f'{tuple(t.shape)} {t.dtype} on {t.device}' + ('' if t.is_contiguous() else ', not contiguous') \
+            if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f'{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device} (got {what})')
+    return t.data_ptr()
+
+
+class NN(ModelAbstr):
+    """k-NN Parareal (Figure_2.py:455-475): the correction is the plain average of the nn nearest
+    neighbours' F - G rows, on the GPU (nngp_knn_mean).  Same constructor
+    (NN(N=..., nn=10)) and name (f'{nn}-NN') as the reference."""
+
+    def __init__(self, *args, **kwargs):
+        self.nn = _nn_count(kwargs.get('nn', 10))
+        self.name = f'{self.nn}-NN'
+        super().__init__(*args, **kwargs)
+        self.k = 0
+        self._dev_xy = None
+        self._host_xy = None
+
+    def fit(self, x, y, k, *args, **kwargs):
+        """Figure_2.py:461-465; a device-resident training set (torch tensors) is kept as it is."""
+        self.k = k
+        if hasattr(x, 'data_ptr'):
+            self._dev_xy, self._host_xy = (x, y), None
+        else:
+            self._dev_xy, self._host_xy = None, (x, y)
+
+    def _host(self):
+        if self._host_xy is None:
+            if self._dev_xy is None:
+                raise AttributeError("'NN' has no training set yet: call fit(x, y, k) first")
+            self._host_xy = tuple(v.detach().cpu().numpy() for v in self._dev_xy)
+        return self._host_xy
+
+    x = property(lambda self: self._host()[0])
+    y = property(lambda self: self._host()[1])
+
+    def device_xy(self):
+        """(X, Y) on the device, uploading a host training set given to fit()."""
+        if self._dev_xy is None:
+            if self._host_xy is None:
+                raise AttributeError("'NN' has no training set yet: call fit(x, y, k) first")
+            self._dev_xy = (_lib.as_device(self._host_xy[0]), _lib.as_device(self._host_xy[1]))
+        X, Y = self._dev_xy
+        if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError(f'the training set must be [rows >= 1][d >= 1] (got x of shape {tuple(X.shape)})')
+        _knn_tensor(X, 'x', X.shape, X.device)
+        _knn_tensor(Y, 'y', X.shape, X.device)
+        return self._dev_xy
+
+    # ---------------------------------------------------------------------------- device path
+    def predict_batch_device(self, Q, counts=None, out=None, idx_out=None, stream=None):
+        """The means of the counts[j] nearest rows for every row of Q [n_q][d], one launch set
+        (nngp_knn_mean): out [len(counts)][n_q][d].  counts defaults to [nn]; each is clamped to the
+        number of training rows (argsort(...)[:nn] on fewer rows keeps them all)."""
+        import torch
+        X, Y = self.device_xy()
+        rows, d = int(X.shape[0]), int(X.shape[1])
+        counts = [self.nn] if counts is None else [_nn_count(c) for c in counts]
+        if not 1 <= len(counts) <= KNN_MAX_COUNTS:
+            raise ValueError(f'{len(counts)} counts: one launch serves 1..{KNN_MAX_COUNTS}')
+        cm = np.array([min(c, rows) for c in counts], dtype=np.int32)
+        if not torch.is_tensor(Q) or Q.dim() != 2:
+            raise ValueError('Q must be a device tensor of shape [n_q][d]')
+        n_q = int(Q.shape[0])
+        q_ptr = _knn_tensor(Q, 'Q', (n_q, d), X.device)
+        if out is None:
+            out = torch.empty((len(cm), n_q, d), dtype=torch.float64, device=X.device)
+        out_ptr = _knn_tensor(out, 'out', (len(cm), n_q, d), X.device)
+        idx_ptr = None if idx_out is None else _knn_tensor(idx_out, 'idx_out', (n_q, int(cm.max())), X.device,
+                                                           torch.int32)
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().nngp_knn_mean(
+            X.data_ptr(), Y.data_ptr(), rows, d, q_ptr, n_q, cm.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            len(cm), out_ptr, idx_ptr, None, None, st))
+        return out
+
+    def predict_device(self, new_x, out=None, bias=None, preds=None, stream=None):
+        """One correction on device tensors: preds, and out = preds + bias when both are given."""
+        import torch
+        X, Y = self.device_xy()
+        rows, d = int(X.shape[0]), int(X.shape[1])
+        if preds is None:
+            preds = torch.empty(d, dtype=torch.float64, device=X.device)
+        if (out is None) != (bias is None):
+            raise ValueError('out and bias go together')
+        cm = (ctypes.c_int32 * 1)(min(self.nn, rows))
+        ptr = lambda t, name: None if t is None else _knn_tensor(t, name, (d,), X.device)
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().nngp_knn_mean(
+            X.data_ptr(), Y.data_ptr(), rows, d, ptr(new_x, 'new_x'), 1, cm, 1, ptr(preds, 'preds'), None,
+            ptr(bias, 'bias'), ptr(out, 'out'), st))
+        return preds
+
+    # ------------------------------------------------------------------------- reference API
+    def predict(self, new_x, prev_F=None, prev_G=None, *args, **kwargs):
+        """Figure_2.py:467-475 (host arrays in, the [d] mean out)."""
+        torch = _lib.require_gpu()
+        q = torch.tensor(np.asarray(new_x, dtype=np.float64).reshape(-1), device='cuda')
+        return self.predict_device(q).cpu().numpy()
+
+    def store(self):
+        """A deep copy for the result dict: host x / y, no device tensors."""
+        if self._dev_xy is not None:
+            self._host()
+        dev, self._dev_xy = self._dev_xy, None
+        try:
+            new = super().store()
+        finally:
+            self._dev_xy = dev
+        return new
+
+    def state_dict(self):
+        st = super().state_dict()
+        st['settings'] = {'nn': self.nn}
+        st['k'] = self.k
+        return st
+
+    def load_state(self, st):
+        super().load_state(st)
+        self.k = st['k']

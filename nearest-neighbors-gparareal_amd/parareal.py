@@ -15,7 +15,8 @@ Per iteration k (parareal.py:301-439):
      iteration (new iterate, coarse column, new D rows, errors) for the result dict and the
      convergence scan (:396-416), which advances I on the host exactly as the reference does.
 The returned dict has the reference's keys ('t', 'u', 'err', 'x', 'D', 'k', 'data_x', 'data_D',
-'timings', 'debug_dict', 'converged', 'conv_int').
+'timings', 'debug_dict', 'converged', 'conv_int'), and 'err_store_mdls' when run(..., comp_mdls=[...])
+asks for the model comparison of Figure_2.py.
 """
 import ctypes
 import json
@@ -26,7 +27,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from .models import ELM, JITTERS, MAX_NEIGHBOURS, BareParareal, GPjax_p, NNGP_p
+from .models import ELM, JITTERS, KNN_MAX_COUNTS, MAX_NEIGHBOURS, NN, BareParareal, GPjax_p, ModelAbstr, NNGP_p
 from .solver import SolverAbstr
 from .systems import ODE
 
@@ -263,6 +264,12 @@ class Parareal():
                                           'map and a 3x3 solve per slice, with nothing to shard; supported: a '
                                           'process group of one rank, or none')
             mdl = ELM(d=self.n, N=self.N, **kwargs)
+        elif model.lower() == 'nn':   # Figure_2.py:455-475, k-NN Parareal
+            if self._world() > 1:
+                raise NotImplementedError("model='nn' runs on one rank: its sweep is a kNN and an average of "
+                                          'at most 64 rows per slice, with nothing to shard; supported: a '
+                                          'process group of one rank, or none')
+            mdl = NN(N=self.N, **kwargs)
         else:
             raise Exception('Not implemented')
         s_time = time.time()
@@ -320,6 +327,8 @@ class Parareal():
             mdl = GPjax_p(n=self.n, N=self.N, worker_pool=GpuPool(), **mst['settings'])
         elif mst['name'] == 'ELM':   # its constructor arguments; the training set is the dump's x / D
             mdl = ELM(d=self.n, N=self.N, **mst['settings'])
+        elif mst['name'].endswith('-NN'):
+            mdl = NN(N=self.N, **mst['settings'])
         else:
             mdl = BareParareal(N=self.N)
         mdl.load_state(mst)
@@ -497,6 +506,12 @@ class Parareal():
                 ctypes.byref(cs), _lib.TABLEAU[solver.G], solver.step_mode, solver.Ng, t_dev.data_ptr(), I, N,
                 U1.data_ptr(), UG1.data_ptr(), Xe.data_ptr(), Ye.data_ptr(), He.data_ptr(), rows_e,
                 min(int(e.m), rows_e), e.poly_degree, e.N, be.data_ptr(), Ce.data_ptr(), ctypes.byref(g_ms), stream))
+        elif isinstance(model, NN):
+            Xn, Yn = model.device_xy()
+            _lib.check(lib.nngp_knn_mean_sweep(
+                ctypes.byref(cs), _lib.TABLEAU[solver.G], solver.step_mode, solver.Ng, t_dev.data_ptr(), I, N,
+                U1.data_ptr(), UG1.data_ptr(), Xn.data_ptr(), Yn.data_ptr(), int(Xn.shape[0]),
+                min(model.nn, int(Xn.shape[0])), None, ctypes.byref(g_ms), stream))
         elif isinstance(model, GPjax_p):
             Xg, alpha, coef = model._dev
             _lib.check(lib.nngp_correction_sweep(
@@ -588,7 +603,8 @@ class Parareal():
         """debug=True (parareal.py:353-392): the same per-slice sweep, keeping every prediction,
         then the 'truth' F(u[i]) - uG_new[i+1] for all slices at once -- ONE batched fine launch
         instead of the reference's N-I serial run_F calls -- and |truth - preds| per slice and
-        coordinate.  Returns (G seconds, pred_err [N-I][n])."""
+        coordinate.  Returns (G seconds, pred_err [N-I][n], truth [N-I][n] on the device and host,
+        the predictions [N-I][n] on the device and host)."""
         lib, n = _lib.lib(), self.n
         P = torch.empty((N - I, n), dtype=torch.float64, device=U1.device)
         zeros = torch.zeros(n, dtype=torch.float64, device=U1.device)
@@ -602,7 +618,7 @@ class Parareal():
             if isinstance(model, NNGP_p):
                 model.predict_device(X, Y, rows, U1[i], th0[j * nf:(j + 1) * nf], out=U1[i + 1],
                                      bias=UG1[i + 1], preds=P[j], stream=stream)
-            elif isinstance(model, ELM):
+            elif isinstance(model, (ELM, NN)):
                 model.predict_device(U1[i], out=U1[i + 1], bias=UG1[i + 1], preds=P[j], stream=stream)
             else:
                 if isinstance(model, GPjax_p):
@@ -616,8 +632,54 @@ class Parareal():
         self.solver.run_F_batch(t_dev[I:N], t_dev[I + 1:N + 1], U1[I:N].contiguous(), out=truth)
         _lib.check(lib.nngp_parareal_update((N - I) * n, truth.data_ptr(), UG1[I + 1:N + 1].data_ptr(), None,
                                             truth.data_ptr(), stream))
-        pred_err = np.abs(truth.cpu().numpy() - P.cpu().numpy())
-        return ev.collect().get('G', 0.0), pred_err
+        truth_h, P_h = truth.cpu().numpy(), P.cpu().numpy()
+        pred_err = np.abs(truth_h - P_h)
+        return ev.collect().get('G', 0.0), pred_err, (truth, truth_h), (P, P_h)
+
+    def _compare_models(self, torch, comp_mdls, I, N, U1, UF, UG, truth, truth_h, stream):
+        """The comparison predictions of one iteration (Figure_2.py:197-203): every model of
+        comp_mdls at every slice's actual starting value U1[i], i = I..N-1, after the sweep.  The
+        queries are independent of each other (nothing here feeds back into the iterate), so all NN
+        models share ONE nngp_knn_mean launch (their counts as the list, groups of 16); an NNGP_p
+        predicts slice by slice with its own draws (its RNG stream is the reference's: one model,
+        slices in order), GPjax_p / ELM through predict_device, any other ModelAbstr through its
+        predict on host arrays.  Returns {id(model): predictions [N-I][n] on the host}."""
+        n, nq = self.n, N - I
+        Q = U1[I:N]
+        preds = {}
+        knn = [m for m in comp_mdls if isinstance(m, NN)]
+        for g0 in range(0, len(knn), KNN_MAX_COUNTS):
+            grp = knn[g0:g0 + KNN_MAX_COUNTS]
+            out = grp[0].predict_batch_device(Q, counts=[m.nn for m in grp], stream=stream).cpu().numpy()
+            for j, m in enumerate(grp):
+                preds[id(m)] = out[j]
+        host = None
+        for m in comp_mdls:
+            if isinstance(m, NN):
+                continue
+            if isinstance(m, (NNGP_p, GPjax_p, ELM)):
+                P = torch.empty((nq, n), dtype=torch.float64, device=U1.device)
+                if isinstance(m, NNGP_p):
+                    X, Y = m._dev_xy
+                    nf = m.n_fits
+                    th0 = torch.tensor(m.draw_thetas(nq), dtype=torch.float64, device=U1.device)
+                    for j in range(nq):
+                        m.predict_device(X, Y, X.shape[0], Q[j], th0[j * nf:(j + 1) * nf], preds=P[j], stream=stream)
+                elif isinstance(m, GPjax_p):
+                    for j in range(nq):
+                        m.predict_device(Q[j], out=P[j], stream=stream)
+                else:
+                    for j in range(nq):
+                        m.predict_device(Q[j], preds=P[j], stream=stream)
+                preds[id(m)] = P.cpu().numpy()
+            else:   # a user's own model, called as the reference calls it (host arrays)
+                if host is None:
+                    host = (Q.cpu().numpy(), UF.cpu().numpy(), UG.cpu().numpy())
+                qh, ufh, ugh = host
+                preds[id(m)] = np.array([np.asarray(m.predict(qh[j].reshape(1, -1), ufh[I + j + 1], ugh[I + j + 1],
+                                                              i=I + j, truth=truth_h[j]), dtype=np.float64).reshape(n)
+                                         for j in range(nq)])
+        return preds
 
     def _correction_sweep_py(self, torch, model, t_dev, I, N, U1, UG1, UF, UG, X, Y, rows, th0, stream):
         """Per-slice Python loop (paged coarse solver only): same launches, issued one by one."""
@@ -632,7 +694,7 @@ class Parareal():
                 j = i - I
                 model.predict_device(X, Y, rows, U1[i], th0[j * nf:(j + 1) * nf], out=U1[i + 1],
                                      bias=UG1[i + 1], stream=stream)
-            elif isinstance(model, (GPjax_p, ELM)):
+            elif isinstance(model, (GPjax_p, ELM, NN)):
                 model.predict_device(U1[i], out=U1[i + 1], bias=UG1[i + 1], stream=stream)
             else:   # (uF - uG_prev) + uG_new   (models.py:82-83, parareal.py:382)
                 _lib.check(lib.nngp_parareal_update(self.n, UF[i + 1].data_ptr(), UG[i + 1].data_ptr(),
@@ -654,6 +716,22 @@ class Parareal():
                 raise NotImplementedError('PararealLight keeps no per-iteration training history')
         if debug and self.process_group is not None:
             raise NotImplementedError('debug mode runs on one rank')
+        # the model comparison of Figure_2.py (:56-61): other models fitted on the driver's training
+        # set every iteration and, in debug mode, asked for every slice's correction
+        comp_mdls = kwargs.get('comp_mdls')
+        err_store_mdls = None
+        if comp_mdls is not None:
+            comp_mdls = list(comp_mdls)
+            for m in comp_mdls:
+                if not isinstance(m, ModelAbstr):
+                    raise TypeError(f'comp_mdls takes ModelAbstr instances (got {type(m).__name__})')
+            if light:
+                raise NotImplementedError('PararealLight does not support comp_mdls (no debug mode)')
+            if self._world() > 1:
+                raise NotImplementedError('comp_mdls runs on one rank: the comparison belongs to debug mode, '
+                                          'which is single-rank; supported: a process group of one rank, or none')
+            err_store_mdls = {m.name: dict() for m in comp_mdls}
+            err_store_mdls['para'] = dict()
         one_step_error, all_pred_err = [], []   # debug (parareal.py:258-262)
         self.spec_hits = []
         # run(..., speculate=, shard_corrections=) override the constructor's settings for this run
@@ -807,6 +885,15 @@ class Parareal():
                 tr_y = np.moveaxis(data_D[I:, :, max(k + 1 - lag_k, 0):k + 1], 1, -1).reshape(-1, n)
                 model.fit_timed(tr_x, tr_y, k=k)
                 Xs, Ds, rows_s = torch.tensor(tr_x, **f64), torch.tensor(tr_y, **f64), tr_x.shape[0]
+            if comp_mdls is not None:   # Figure_2.py:164-168, on the driver's training set
+                for m in comp_mdls:
+                    err_store_mdls[m.name][k] = list()
+                    err_store_mdls['para'][k] = list()
+                    if isinstance(m, (NN, NNGP_p, GPjax_p, ELM)):
+                        m.fit_timed(Xs[:rows_s], Ds[:rows_s], k=k, data_x=data_x, data_y=data_D)
+                    else:   # a user's own model gets host arrays, as in the reference
+                        m.fit_timed(Xs[:rows_s].cpu().numpy(), Ds[:rows_s].cpu().numpy(), k=k, data_x=data_x,
+                                    data_y=data_D)
             if is_nngp:
                 draws = torch.from_numpy(model.draw_thetas(N - I))
                 if th_pin is None or th_pin.numel() < draws.numel():
@@ -818,8 +905,8 @@ class Parareal():
                 th0.view(-1).copy_(th_pin[:draws.numel()], non_blocking=True)
             e_loop = ev.start()
             if debug:
-                g_s, pred_err = self._correction_sweep_debug(torch, model, t_dev, I, N, Uk1, UGk1, UF, UGk, Xs, Ds,
-                                                             rows_s, th0 if is_nngp else None, stream)
+                g_s, pred_err, truth, P = self._correction_sweep_debug(
+                    torch, model, t_dev, I, N, Uk1, UGk1, UF, UGk, Xs, Ds, rows_s, th0 if is_nngp else None, stream)
                 if verbose == 'v':
                     print(f'Avg error {np.mean(pred_err, 0)}, Max. error {np.max(pred_err, 0)}')
                 all_pred_err.append(pred_err)
@@ -827,6 +914,13 @@ class Parareal():
                 g_s = self._correction_sweep(torch, model, t_dev, I, N, Uk1, UGk1, UF, UGk, Xs, Ds, rows_s,
                                              th0 if is_nngp else None, stream)
             ev.stop(e_loop, 'loop')
+            if debug and comp_mdls is not None:   # Figure_2.py:197-203, outside the driver model's time
+                cmp_preds = self._compare_models(torch, comp_mdls, I, N, Uk1, UF, UGk, truth[0], truth[1], stream)
+                with np.errstate(divide='ignore'):   # an exact hit is -inf, as in the reference
+                    log_err = lambda pr: [float(np.max(np.log10(np.abs(truth[1][j] - pr[j])))) for j in range(N - I)]
+                    for m in comp_mdls:
+                        err_store_mdls[m.name][k] = log_err(cmp_preds[id(m)])
+                    err_store_mdls['para'][k] = log_err(P[1])
             # ONE device->host copy per iteration: the new iterate (the reference's u[:, :, k+1]),
             # the new coarse column (NaN guard, checkpoint), the new D rows and the slice errors
             # ||u^{k+1}_p - u^k_p||_inf (parareal.py:402-403; torch.amax propagates NaN as np.max).
@@ -898,9 +992,12 @@ class Parareal():
         if light:   # (parareal.py:1057-1059): the newest iterate only, no data_x/data_D
             return {'t': t, 'u': u[:, :, last].copy(), 'err': err[:, :k + 1], 'x': x, 'D': D, 'k': k + 1,
                     'timings': timings, 'debug_dict': {}, 'converged': I == N, 'conv_int': conv_int}
-        return {'t': t, 'u': u[:, :, :k + 1], 'err': err[:, :k + 1], 'x': x, 'D': D, 'k': k + 1,
-                'data_x': data_x[..., :k + 1], 'data_D': data_D[..., :k + 1], 'timings': timings,
-                'debug_dict': debug_dict, 'converged': I == N, 'conv_int': conv_int}
+        out = {'t': t, 'u': u[:, :, :k + 1], 'err': err[:, :k + 1], 'x': x, 'D': D, 'k': k + 1,
+               'data_x': data_x[..., :k + 1], 'data_D': data_D[..., :k + 1], 'timings': timings,
+               'debug_dict': debug_dict, 'converged': I == N, 'conv_int': conv_int}
+        if err_store_mdls is not None:   # Figure_2.py:295-298
+            out['err_store_mdls'] = err_store_mdls
+        return out
 
 
 class PararealLight(Parareal):
