@@ -287,6 +287,93 @@ __device__ __forceinline__ double step_update(double u, const double *k, int c) 
     return u + acc;
 }
 
+// The lane-group kernel's folded tableau (rk_group_kernel only; the lane, field and pair kernels
+// keep stage_input and step_update above).  Where some row's single non-zero entry is a power of
+// two a = A[s][j] != 1 (RK4: u + 0.5 k0, u + 0.5 k1), column j's k is stored pre-scaled,
+// k'_j = (a h) o_j -- the one multiply h o_j costs -- and that stage's input is u + k'_j, an add
+// instead of a multiply and an add.  Scaling by a power of two commutes with rounding,
+// RN(a RN(h o)) = RN((a h) o), whenever the products are normal or exact zeros (signs included),
+// so k'_j is bitwise a k_j; every other coefficient on column j, B[j] included, is divided by a
+// at compile time (an exact rescaling), so each term c k_j = (c/a) k'_j has the same real product
+// and the same rounding, and the sums keep stage_input's and step_update's order.  Where h o is
+// subnormal (|k| < 2^-1022) the two forms can differ in the last denormal bit.
+// The contracted build keeps the unfolded tableau: there u + k' with k' = (a h) o would contract to
+// fma(a h, o, u) and skip k's rounding, where u + a k contracts to fma(a, k, u) and keeps it --
+// another result (TomLab N = 256 converges in another K, tests/test_gpu_contract.py).
+#ifdef NNGP_RK_FMA
+constexpr bool FOLD_TABLEAU = false;
+#else
+constexpr bool FOLD_TABLEAU = true;
+#endif
+__host__ __device__ constexpr bool fold_pow2(double a) {
+    if (!(a > 0.0)) return false;
+    while (a < 1.0) a *= 2.0;
+    while (a >= 2.0) a *= 0.5;
+    return a == 1.0;
+}
+template <typename T>
+__host__ __device__ constexpr double fold_col_scale(int j) {
+    for (int s = j + 1; s < T::S; s++) {
+        int nz = 0;
+        for (int q = 0; q < s; q++) nz += T::A[s][q] != 0.0;
+        const double a = T::A[s][j];
+        if (nz == 1 && a != 0.0 && a != 1.0 && fold_pow2(a)) return a;
+    }
+    return 1.0;
+}
+template <typename T>
+__host__ __device__ constexpr double fold_a(int s, int j) { return T::A[s][j] / fold_col_scale<T>(j); }
+template <typename T>
+__host__ __device__ constexpr double fold_b(int j) { return T::B[j] / fold_col_scale<T>(j); }
+static_assert(fold_col_scale<Tableau<1>>(0) == 1.0, "RK1: nothing to fold");
+static_assert(fold_col_scale<Tableau<2>>(0) == 0.5 && fold_col_scale<Tableau<2>>(1) == 1.0 &&
+              fold_a<Tableau<2>>(1, 0) == 1.0 && fold_b<Tableau<2>>(0) == 0.0, "RK2: k0 halved");
+static_assert(fold_col_scale<Tableau<4>>(0) == 0.5 && fold_col_scale<Tableau<4>>(1) == 0.5 &&
+              fold_col_scale<Tableau<4>>(2) == 1.0 && fold_col_scale<Tableau<4>>(3) == 1.0 &&
+              fold_a<Tableau<4>>(1, 0) == 1.0 && fold_a<Tableau<4>>(2, 1) == 1.0 &&
+              fold_a<Tableau<4>>(3, 2) == 1.0 && fold_b<Tableau<4>>(0) == 2 * Tableau<4>::B[0] &&
+              fold_b<Tableau<4>>(1) == 2 * Tableau<4>::B[1] && fold_b<Tableau<4>>(2) == Tableau<4>::B[2],
+              "RK4: k0 and k1 halved, their update weights doubled");
+static_assert(fold_col_scale<Tableau<8>>(0) == 0.5 && fold_col_scale<Tableau<8>>(1) == 1.0 &&
+              fold_a<Tableau<8>>(1, 0) == 1.0 && fold_a<Tableau<8>>(2, 0) == 0.5 &&
+              fold_a<Tableau<8>>(3, 0) == 2 * Tableau<8>::A[3][0] && fold_b<Tableau<8>>(0) == 2 * Tableau<8>::B[0],
+              "RK8: k0 halved (row 1), column 0's other entries and B[0] doubled");
+
+// stage s's step size: (a h) for a pre-scaled column (loop-invariant in fixed-step mode), else h
+template <typename T>
+__device__ __forceinline__ double fold_h(int s, double h) {
+    return fold_col_scale<T>(s) == 1.0 ? h : fold_col_scale<T>(s) * h;
+}
+// one term c k' of a folded sum: no multiply where the rescaled coefficient is 1
+__device__ __forceinline__ double fold_term(double c, double kp) { return c == 1.0 ? kp : c * kp; }
+// stage_input and step_update on the pre-scaled k' (one component per lane: k[j])
+template <typename T>
+__device__ __forceinline__ double fold_stage_input(int s, double u, const double *k) {
+    double t = 0.0;
+    bool first = true;
+#pragma unroll
+    for (int j = 0; j < T::S; j++) {
+        if (j >= s || T::A[s][j] == 0.0) continue;
+        const double v = fold_term(fold_a<T>(s, j), k[j]);
+        t = first ? v : t + v;
+        first = false;
+    }
+    return first ? u : u + t;
+}
+template <typename T>
+__device__ __forceinline__ double fold_step_update(double u, const double *k) {
+    double acc = 0.0;
+    bool first = true;
+#pragma unroll
+    for (int s = 0; s < T::S; s++) {
+        if (T::B[s] == 0.0) continue;
+        const double v = fold_term(fold_b<T>(s), k[s]);
+        acc = first ? v : acc + v;
+        first = false;
+    }
+    return u + acc;
+}
+
 // FIXED:    h = dt = (t1-t0)/steps (RK.py:103).
 // LINSPACE: step n of slice i is step j = j0 + n of the grid np.linspace(t0, t1, gsteps+1):
 //           t[j] = j*gstep + t0 (gstep = (t1-t0)/gsteps), t[gsteps] = t1, h = t[j+1]-t[j]

@@ -76,7 +76,12 @@ __global__ void __launch_bounds__(64) rk_poly_lane_kernel(PolyLaneArgs args, int
 // with one wave per SIMD): 0.1725 -> 0.158 us/step (profiles/r07/bench_before_after.txt); then
 // RK4's three u2/mu divisions per step as one, in spare lanes of the component's bank (73), and
 // four steps per iteration: 0.143 us/step (profiles/r08/bench_before_after.txt).
-// Bitwise the lane kernel: each component is rounded by the same expression in the same order.
+// Every group kernel since round 9: the tableau's power-of-two entry folded into h (k'_j = (a h) o_j
+// stored, u + k'_j used, the column's other coefficients rescaled at compile time: fold_* in
+// nngp_rk_dev.h; two VALU fewer per RK4 step, Hopf 71) and sixteen steps per iteration for the
+// tableaux of up to four stages (profiles/r09/bench_before_after.txt).
+// Bitwise the lane kernel: each component is rounded by the same expression in the same order
+// (the fold: by an expression with the same real value at every rounding, for normal products).
 // ---------------------------------------------------------------------------------------------
 template <int CTRL>
 __device__ __forceinline__ double quad_mov(double v) {
@@ -512,24 +517,33 @@ __global__ void __launch_bounds__(64) rk_group_kernel(LaneArgs args, int n_slice
         constexpr double a0 = group_batch_coef<T>(0), a1 = group_batch_coef<T>(1);
         GroupSys<SYS>::batch_init(gst, tid % 16, a0 * kc, a1 * kc);
     }
+    // The tableau is folded (nngp_rk_dev.h, fold_*): k[j] holds k'_j = (a_j h) o_j, the one multiply
+    // h o_j costs, and the stage inputs and the update take the rescaled coefficients (RK4:
+    // u + k'0, u + k'1, u + k2 and (1/3) k'0 + (2/3) k'1 + (1/3) k2 + (1/6) k3).  The batched
+    // offsets above stay a*RN(dt*o), the values the reference forms.  (Exact build only: the
+    // contracted build keeps stage_input and step_update, FOLD_TABLEAU in nngp_rk_dev.h.)
     auto step = [&](int64_t n) __attribute__((always_inline)) {
         const double h = LINSPACE ? grid.next(n, T0, T1, dt) : dt;
 #pragma unroll
         for (int s = 0; s < S; s++) {
             double tmp;
-            if constexpr (BATCH) tmp = s == 0 ? u + gst.OFF : stage_input<T, 1>(s, u, k, 0);
+            if constexpr (BATCH) tmp = s == 0 ? u + gst.OFF : fold_stage_input<T>(s, u, k);
+            else if constexpr (FOLD_TABLEAU) tmp = fold_stage_input<T>(s, u, k);
             else tmp = stage_input<T, 1>(s, u, k, 0);
             double o;
             if constexpr (NORM) o = group_f<SYS, T, BATCH>(s, (tmp + 1) * hw + mn, gst, one, args) * sc;
             else o = group_f<SYS, T, BATCH>(s, tmp, gst, one, args);
-            k[s] = h * o;
+            if constexpr (FOLD_TABLEAU) k[s] = fold_h<T>(s, h) * o;
+            else k[s] = h * o;
         }
-        u = step_update<T, 1>(u, k, 0);
+        if constexpr (FOLD_TABLEAU) u = fold_step_update<T>(u, k);
+        else u = step_update<T, 1>(u, k, 0);
     };
     // UNROLL steps per iteration and a remainder loop: the step is one wave's instruction issue with
-    // no other wave on the SIMD to cover the loop's taken branch.  Four for
-    // the tableaux of up to four stages; RK8's eleven stay at two (code size).
-    constexpr int UNROLL = S <= 4 ? 4 : 2;
+    // no other wave on the SIMD to cover the loop's taken branch.  Sixteen
+    // for the tableaux of up to four stages (RK4: about 10 KB of loop body, inside the instruction
+    // cache); RK8's eleven stay at two (code size).
+    constexpr int UNROLL = S <= 4 ? 16 : 2;
     int64_t n = 0;
     for (; n + (UNROLL - 1) < steps; n += UNROLL) {
 #pragma unroll
