@@ -360,8 +360,9 @@ __device__ __forceinline__ double fold_stage_input(int s, double u, const double
     }
     return first ? u : u + t;
 }
+// (fold_step_sum: the step's increment alone, for a component whose k are known beforehand)
 template <typename T>
-__device__ __forceinline__ double fold_step_update(double u, const double *k) {
+__device__ __forceinline__ double fold_step_sum(const double *k) {
     double acc = 0.0;
     bool first = true;
 #pragma unroll
@@ -371,10 +372,14 @@ __device__ __forceinline__ double fold_step_update(double u, const double *k) {
         acc = first ? v : acc + v;
         first = false;
     }
-    return u + acc;
+    return acc;
+}
+template <typename T>
+__device__ __forceinline__ double fold_step_update(double u, const double *k) {
+    return u + fold_step_sum<T>(k);
 }
 
-// FIXED:    h = dt = (t1-t0)/steps (RK.py:103).
+// FIXED:   h = dt = (t1-t0)/steps (RK.py:103).
 // LINSPACE: step n of slice i is step j = j0 + n of the grid np.linspace(t0, t1, gsteps+1):
 //           t[j] = j*gstep + t0 (gstep = (t1-t0)/gsteps), t[gsteps] = t1, h = t[j+1]-t[j]
 //           (RK.py:91-99, 121; new_lib.py:87-137).  j0 = 0, gsteps = steps is the per-slice grid;

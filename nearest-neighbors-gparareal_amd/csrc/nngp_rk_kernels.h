@@ -80,6 +80,14 @@ __global__ void __launch_bounds__(64) rk_poly_lane_kernel(PolyLaneArgs args, int
 // stored, u + k'_j used, the column's other coefficients rescaled at compile time: fold_* in
 // nngp_rk_dev.h; two VALU fewer per RK4 step, Hopf 71) and sixteen steps per iteration for the
 // tableaux of up to four stages (profiles/r09/bench_before_after.txt).
+// Hopf RK4 in fixed-step mode since round 13: the time track (GroupSys<HOPF>::track_div, f_take).
+// u2 advances by the same INC every step, so the u2/mu quotients of four steps -- twelve of them,
+// one per lane of a register of its own -- come from one de-normalisation and one division per
+// four steps, formed a pass ahead from instructions that read nothing of the u0/u1 chain and
+// stand in its wait states; every stage, stage 0 included, takes its quotient with the move it
+// issues anyway, and the sixteen-step loop ends on a scalar compare (69.75 VALU per step, round
+// 9: 71.06).  With the track's instructions as the fillers round 9 lacked, three stages per four
+// steps fuse the second subtraction of g as well (f_take2): 69.19 (profiles/r13/).
 // Bitwise the lane kernel: each component is rounded by the same expression in the same order
 // (the fold: by an expression with the same real value at every rounding, for normal products).
 // ---------------------------------------------------------------------------------------------
@@ -164,10 +172,9 @@ template <> struct GroupSys<NNGP_SYS_HOPF> {     // systems.py:148-154, as LaneS
 #else
     struct St {
         double Q, A2, B2, P, S, M;
-        double OFF, q;   // the lane-batched form's (f_batched below); unused otherwise
     };
     __device__ static St init(int c) {
-        return St{0.0, 0.0, 0.0, c == 2 ? 1.0 : 0.0, c == 0 ? -1.0 : 1.0, -1.0, -0.0, 0.0};
+        return St{0.0, 0.0, 0.0, c == 2 ? 1.0 : 0.0, c == 0 ? -1.0 : 1.0, -1.0};
     }
     // q = x/mu (div_const) and sq = x*x in every lane, then P, Q, B2 in an order that leaves two
     // instructions between each register's write and its DPP read: q -> (sq, P) -> Q;
@@ -215,59 +222,114 @@ template <> struct GroupSys<NNGP_SYS_HOPF> {     // systems.py:148-154, as LaneS
         }
         return o;
     }
-    // Lane-batched u2/mu (RK4 in fixed-step mode: group_batch_slots below).
-    // Bank 2's f is the constant 1, so k2 = h*sc2 is the same at every stage of every step of the
-    // slice, and the time inputs of stages 1..S-1 -- u2 + RN(a*k2), one `a` per stage, two distinct
-    // ones in RK4 -- are known when the step starts.  Bank 2 has four lanes and needs one: lane 8
-    // keeps the component, lanes 9 and 10 get the two offsets added to stage 0's input (OFF: a*k2
-    // there, -0.0 in every other lane, and x + (-0.0) is x bit for bit, zeros of either sign and NaN
-    // included), run stage 0's own de-normalisation and division on them -- the roundings of the
-    // reference's later stages, one lane over -- and stage 0's q register, carried, holds all three
-    // quotients.  Stages 1..3 then take theirs with the move they need anyway (row_newbcast:9, 9
-    // and 10 instead of 8) and skip the division: 12 + 9 + 9 + 9 VALU and no s_nop.  The state u is
-    // not touched: lanes 9 and 10 of stage 0 feed nothing but q (their g is +-0 and their f is 1 for
-    // any finite x), so lanes 9..11 keep carrying lane 8's u2.
+    // The time track (RK4 in fixed-step mode: group_tracks below).
+    // Bank 2's f is the constant 1, so in fixed-step mode its four k are the same constants at every
+    // step of the slice and u2 advances by the same INC = RN(sum b k) per step, whatever u0 and u1
+    // do: every time input of the next four steps -- u2_j at stage 0, u2_j + RN(a k2) at the later
+    // stages, two distinct a in RK4 -- is known before those steps start.  A register of its own,
+    // the track, holds them for four steps at once: lane 4j + r of a slice's 16 carries step j's u2
+    // (j = 0..3, the same in the four lanes of a j) and, after one add of the per-lane constant OFFr
+    // (-0.0, RN(a0 k2), RN(a1 k2) for r = 0, 1, 2; x + (-0.0) is x bit for bit, zeros of either sign
+    // included), one de-normalisation with component 2's constants and ONE Markstein division, the
+    // quotient of step j's stage 0 (r = 0), stages 1 and 2 (r = 1) and stage 3 (r = 2): the roundings
+    // the reference performs on that stage's time input, 12 of them in one pass.  Every stage of
+    // the four steps, stage 0 included, is a take stage: it fetches its u2/mu with the bank-masked
+    // `row_newbcast:L` move it needs anyway and divides nothing.  The track advances by four
+    // dependent adds of INC per batch, the sequential roundings lane 8 performs on u, so it reads
+    // nothing of the u0/u1 chain inside the loop and its 11 instructions per four steps (8 without
+    // de-normalisation) are free to stand wherever that chain leaves a wait state.  The state u is
+    // advanced in bank 2 as ever (P = 1, Q = B2 = 0 there).
     // Wait states of a take stage (every VGPR a DPP op reads written at least two instructions
     // earlier): x may be written by the instruction before the statement, so its first DPP read is
-    // the third op, behind x*x and the move of the carried q; q was written by stage 0's statement
-    // and Q by the previous statement's fused op, which its three-op tail follows, and nothing
-    // between two statements writes either (no other code names them); sq -> (Q, P) -> B2;
-    // Q -> (P, B2) -> fused; P -> (B2, fused) -> P.
-    __device__ static void batch_init(St &s, int lane, double off0, double off1) {
-        s.OFF = lane == 9 ? off0 : lane == 10 ? off1 : -0.0;
-        // opaque from here on, so that the step's u + OFF stays one add: x + (-0.0) -> x is a legal
-        // fold that would move the add into the select, per step (the present compiler gives the
-        // same loop without this)
-        asm("" : "+v"(s.OFF));
-    }
-#define NNGP_HOPF_TAKE(L)                                                          \
-    asm("v_mul_f64 %[sq], %[x], %[x]\n\t"                                          \
-        "v_mov_b64_dpp %[Q], %[q] row_newbcast:" L " row_mask:0xf bank_mask:0x3\n\t" \
-        "v_mov_b64_dpp %[P], %[x] row_newbcast:4 row_mask:0xf bank_mask:0x1\n\t"    \
-        "v_mov_b64_dpp %[B2], %[sq] row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"  \
-        "v_fmac_f64_dpp %[Q], %[sq], %[M] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t" \
-        "v_mov_b64_dpp %[P], %[x] row_newbcast:0 row_mask:0xf bank_mask:0x2\n\t"    \
-        NNGP_HOPF_TAIL("Q")                                                        \
-        : [o] "=&v"(o), [sq] "=&v"(sq), [t] "=&v"(t), [Q] "+v"(s.Q), [B2] "+v"(s.B2), [P] "+v"(s.P) \
-        : [x] "v"(x), [q] "v"(s.q), [S] "v"(s.S), [M] "v"(s.M))
-    // slot: -1 = stage 0 (divides in every lane), 0 / 1 = the quotient of lane 9 / 10
-    __device__ static double f_batched(double x, St &s, int slot, const LaneArgs &a) {
-        double o, sq, e, t;
-        if (slot < 0) {
-            asm(NNGP_HOPF_HEAD
-                "v_fmac_f64_dpp %[Q], %[sq], %[M] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"
-                NNGP_HOPF_TAIL("Q")
-                : [o] "=&v"(o), [sq] "=&v"(sq), [t] "=&v"(t), [e] "=&v"(e), [q] "=&v"(s.q), [Q] "+v"(s.Q),
-                  [B2] "+v"(s.B2), [P] "+v"(s.P)
-                : [x] "v"(x), [S] "v"(s.S), [M] "v"(s.M), [b] "v"(a.param[0]), [r] "v"(a.rparam0));
-        } else if (slot == 0) {
-            NNGP_HOPF_TAKE("9");
-        } else {
-            NNGP_HOPF_TAKE("10");
-        }
+    // the third op, behind x*x and the move of the quotient; the quotient register is written by
+    // the first instruction of track_div's statement, whose second (one of the track's adds)
+    // follows it, and x*x stands in front of the move that reads it; Q was written by the previous
+    // statement's fused op, which its three-op tail follows (before the first statement:
+    // track_settle), and nothing between two statements writes Q, B2 or P (no other code names
+    // them); sq -> (Q, P) -> B2; Q -> (P, B2) -> fused; P -> (B2, fused) -> P.
+    static constexpr int TC = 2;   // the time component
+    // the last op of the track's division and one of its adds: a quotient register is never
+    // written by the instruction in front of a take statement
+    // x/mu as div_const forms it, q = RN(x r), fma(fma(-q, mu, x), r, q); tu advances by inc
+    __device__ static double track_div(double x, double &tu, double inc, const LaneArgs &a) {
+        const double q = x * a.rparam0, e = fma(-q, a.param[0], x);
+        double o;
+        asm("v_fma_f64 %[o], %[e], %[r], %[q]\n\t"
+            "v_add_f64 %[tu], %[tu], %[inc]"
+            : [o] "=&v"(o), [tu] "+v"(tu)
+            : [e] "v"(e), [q] "v"(q), [r] "v"(a.rparam0), [inc] "v"(inc));
         return o;
     }
-#undef NNGP_HOPF_TAKE
+    // before the first take statement: whatever initialised the carried registers is two wait
+    // states away
+    __device__ static void track_settle(St &s) {
+        asm volatile("s_nop 1" : "+v"(s.Q), "+v"(s.B2), "+v"(s.P), "+v"(s.S), "+v"(s.M));
+    }
+    // lane L of the track's quotients qt into Q, then the round-7 right-hand side
+    template <int L>
+    __device__ static double f_take(double x, St &s, double qt) {
+        double o, sq, t;
+        asm("v_mul_f64 %[sq], %[x], %[x]\n\t"
+            "v_mov_b64_dpp %[Q], %[q] row_newbcast:%[L] row_mask:0xf bank_mask:0x3\n\t"
+            "v_mov_b64_dpp %[P], %[x] row_newbcast:4 row_mask:0xf bank_mask:0x1\n\t"
+            "v_mov_b64_dpp %[B2], %[sq] row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"
+            "v_fmac_f64_dpp %[Q], %[sq], %[M] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"
+            "v_mov_b64_dpp %[P], %[x] row_newbcast:0 row_mask:0xf bank_mask:0x2\n\t"
+            NNGP_HOPF_TAIL("Q")
+            : [o] "=&v"(o), [sq] "=&v"(sq), [t] "=&v"(t), [Q] "+v"(s.Q), [B2] "+v"(s.B2), [P] "+v"(s.P)
+            : [x] "v"(x), [q] "v"(qt), [S] "v"(s.S), [M] "v"(s.M), [L] "n"(L));
+        return o;
+    }
+    // A take stage with BOTH subtractions of g fused: Q <- fma(bcast(u1^2), M, Q) by a second
+    // `v_fmac_f64_dpp row_newbcast:4` on the same square, in place of B2's move and the add -- the
+    // correctly rounded (q - u0^2) - u1^2 by the argument above (bank 2 keeps Q = +0, the 0 - 0 of
+    // the unfused form).  Each fused op needs its accumulator written two instructions earlier,
+    // and the chain has nothing of its own to put there (rounds 7 and 9): the
+    // two slots F1 and F2 take two instructions of the track, which read nothing of the chain and
+    // are written to tk, a register set no DPP op reads.  8 chain ops instead of 9.
+    // Wait states: sq -> (Q, P, F1) -> fused; Q -> (P, F1) -> fused -> (P, F2) -> fused; P ->
+    // (F1, fused) -> P; x and the quotient as in f_take; B2 is not touched.  The statement ends
+    // with two plain ops behind its last write of Q, so the next statement's move into Q is safe.
+    struct Tk { double x, q, e; };   // the track's division in flight: its input, RN(x r), the residual
+#define NNGP_HOPF_TAKE2(F1, F2)                                                       \
+    asm("v_mul_f64 %[sq], %[x], %[x]\n\t"                                             \
+        "v_mov_b64_dpp %[Q], %[q] row_newbcast:%[L] row_mask:0xf bank_mask:0x3\n\t"   \
+        "v_mov_b64_dpp %[P], %[x] row_newbcast:4 row_mask:0xf bank_mask:0x1\n\t"      \
+        F1 "\n\t"                                                                     \
+        "v_fmac_f64_dpp %[Q], %[sq], %[M] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t" \
+        "v_mov_b64_dpp %[P], %[x] row_newbcast:0 row_mask:0xf bank_mask:0x2\n\t"      \
+        F2 "\n\t"                                                                     \
+        "v_fmac_f64_dpp %[Q], %[sq], %[M] row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t" \
+        "v_mul_f64 %[t], %[x], %[Q]\n\t"                                              \
+        "v_fma_f64 %[o], %[S], %[P], %[t]"                                            \
+        : [o] "=&v"(o), [sq] "=&v"(sq), [t] "=&v"(t), [Q] "+v"(s.Q), [P] "+v"(s.P),   \
+          [tx] "+v"(tk.x), [tq] "+v"(tk.q), [te] "+v"(tk.e)                           \
+        : [x] "v"(x), [q] "v"(qt), [S] "v"(s.S), [M] "v"(s.M), [L] "n"(L), [tu] "v"(tu), \
+          [offr] "v"(offr), [hw2] "v"(hw2), [mn2] "v"(mn2), [r] "v"(a.rparam0), [b] "v"(a.param[0]))
+    // K: which two of the track's instructions the statement carries.  Normalised: 1 = tu + OFFr
+    // and + 1, 2 = * hw and + mn, 3 = x r and the residual.  Identity: 4 = tu + OFFr and x r.
+    template <int L, int K>
+    __device__ static double f_take2(double x, St &s, double qt, Tk &tk, double tu, double offr, double hw2,
+                                     double mn2, const LaneArgs &a) {
+        static_assert(K >= 1 && K <= 4, "one of the four pairs");
+        double o, sq, t;
+        if constexpr (K == 1) NNGP_HOPF_TAKE2("v_add_f64 %[tx], %[tu], %[offr]", "v_add_f64 %[tx], %[tx], 1.0");
+        else if constexpr (K == 2) NNGP_HOPF_TAKE2("v_mul_f64 %[tx], %[tx], %[hw2]", "v_add_f64 %[tx], %[tx], %[mn2]");
+        else if constexpr (K == 3) NNGP_HOPF_TAKE2("v_mul_f64 %[tq], %[tx], %[r]", "v_fma_f64 %[te], -%[tq], %[b], %[tx]");
+        else NNGP_HOPF_TAKE2("v_add_f64 %[tx], %[tu], %[offr]", "v_mul_f64 %[tq], %[tx], %[r]");
+        return o;
+    }
+    // the end of the division the fused take stages left in tk, and one of the track's adds (as
+    // track_div: the quotient register is not written by the last instruction of the statement)
+    __device__ static double track_fin(const Tk &tk, double &tu, double inc, const LaneArgs &a) {
+        double o;
+        asm("v_fma_f64 %[o], %[e], %[r], %[q]\n\t"
+            "v_add_f64 %[tu], %[tu], %[inc]"
+            : [o] "=&v"(o), [tu] "+v"(tu)
+            : [e] "v"(tk.e), [q] "v"(tk.q), [r] "v"(a.rparam0), [inc] "v"(inc));
+        return o;
+    }
+#undef NNGP_HOPF_TAKE2
 #undef NNGP_HOPF_HEAD
 #undef NNGP_HOPF_TAIL
 #endif
@@ -366,13 +428,12 @@ static_assert(group_repeat_count<Tableau<1>>() == 0 && group_repeat_count<Tablea
 // Lane batching of a component whose f is the same constant at every stage (all its k_j bitwise
 // equal, k): its input at stage 0 is u, and at a stage whose tableau row has a single non-zero
 // entry a it is u + RN(a*k) whichever k_j the entry is on, so what a group RHS derives from those
-// inputs can be computed for all of them at stage 0, in spare lanes of the component's bank (slot =
-// the index of a among the tableau's distinct such entries, in order of appearance; a repeating
-// stage has its predecessor's).  group_batch_slot: -1 for stage 0, the slot, or -2 where the input
-// has another form (a later row with none or several entries).  A group RHS with an f_batched
-// batches when the tableau has exactly the two slots the form is built for: RK4 (a = 1/2 at
-// stages 1 and 2, a = 1 at stage 3); not RK1 and RK2 (no and one slot) nor RK8 (row 2 has two
-// entries), which keep the form above.
+// inputs can be computed for all of them at once, in lanes of their own (slot = the index of a
+// among the tableau's distinct such entries, in order of appearance; a repeating stage has its
+// predecessor's).  group_batch_slot: -1 for stage 0, the slot, or -2 where the input has another
+// form (a later row with none or several entries).  The time track (group_tracks below) is built
+// for exactly two slots: RK4 (a = 1/2 at stages 1 and 2, a = 1 at stage 3); not RK1 and RK2 (no
+// and one slot) nor RK8 (row 2 has two entries), which keep the form above.
 template <typename T>
 __host__ __device__ constexpr double group_batch_entry(int s) {   // the single entry of row s, or 0.0
     double a = 0.0;
@@ -418,6 +479,30 @@ static_assert(group_batch_slots<Tableau<4>>() == 2 && group_batch_slot<Tableau<4
               "RK4: u + k/2 at stages 1 and 2, u + k at stage 3");
 static_assert(group_batch_slots<Tableau<1>>() == 0 && group_batch_slots<Tableau<2>>() == 1 &&
               group_batch_slots<Tableau<8>>() == -1, "RK1, RK2, RK8: not lane-batched");
+// The time track: a group RHS with a track_div keeps the constant component's inputs of four steps
+// at once (GroupSys<HOPF>) when the tableau has exactly the two slots the form is built for, so
+// that lane 4j + slot + 1 of the track holds step j's stage input of that slot (slot -1: stage 0).
+template <typename T>
+__host__ __device__ constexpr bool group_track_tableau() { return group_batch_slots<T>() == 2; }
+static_assert(group_track_tableau<Tableau<4>>(), "RK4: the time track applies");
+static_assert(!group_track_tableau<Tableau<1>>() && !group_track_tableau<Tableau<2>>() &&
+              !group_track_tableau<Tableau<8>>(), "RK1, RK2, RK8: no time track");
+constexpr int TRACK_STEPS = 4;   // steps per pass of the track: 4 lanes per step, 16 per slice
+template <class GS, typename T, class = void> struct group_tracks {
+    static constexpr bool value = false;
+};
+template <class GS, typename T> struct group_tracks<GS, T, std::void_t<decltype(&GS::track_div)>> {
+    static constexpr bool value = group_track_tableau<T>();
+};
+
+// stage s of the group RHS: a field with carried state (St) is told whether the stage repeats and
+// whether the next one will (never both: what a stage keeps, the next uses up)
+template <int SYS, typename T, typename G>
+__device__ __forceinline__ double group_f(int s, double x, G &gst, double one, const LaneArgs &args) {
+    if constexpr (std::is_same_v<G, int>) return GroupSys<SYS>::f(x, gst, one, args);
+    else return GroupSys<SYS>::f(x, gst, group_stage_repeats<T>(s), group_stage_repeats<T>(s + 1), args);
+}
+// stage s of step J of a pass of the time track: the RHS takes lane 4 J + slot + 1 of the quotients
 template <typename T> struct GroupBatchSlots {
     int slot[T::S];
 };
@@ -427,24 +512,14 @@ constexpr GroupBatchSlots<T> group_batch_table() {
     for (int s = 0; s < T::S; s++) t.slot[s] = group_batch_slot<T>(s);
     return t;
 }
-template <class GS, typename T, class = void> struct group_batches {
-    static constexpr bool value = false;
-};
-template <class GS, typename T> struct group_batches<GS, T, std::void_t<decltype(&GS::f_batched)>> {
-    static constexpr bool value = group_batch_slots<T>() == 2;
-};
-
-// stage s of the group RHS: a field with carried state (St) is told the stage's slot where it
-// batches (BATCH), else whether the stage repeats and whether the next one will (never both: what
-// a stage keeps, the next uses up)
-template <int SYS, typename T, bool BATCH, typename G>
-__device__ __forceinline__ double group_f(int s, double x, G &gst, double one, const LaneArgs &args) {
-    if constexpr (std::is_same_v<G, int>) return GroupSys<SYS>::f(x, gst, one, args);
-    else if constexpr (BATCH) {
-        constexpr GroupBatchSlots<T> tab = group_batch_table<T>();   // a constant once s is unrolled
-        return GroupSys<SYS>::f_batched(x, gst, tab.slot[s], args);
-    }
-    else return GroupSys<SYS>::f(x, gst, group_stage_repeats<T>(s), group_stage_repeats<T>(s + 1), args);
+template <int SYS, typename T, int J, typename G>
+__device__ __forceinline__ double group_f_track(int s, double x, G &gst, double qt) {
+    static_assert(J >= 0 && J < TRACK_STEPS, "a pass of the track holds TRACK_STEPS steps");
+    constexpr GroupBatchSlots<T> tab = group_batch_table<T>();   // a constant once s is unrolled
+    const int slot = tab.slot[s];
+    if (slot < 0) return GroupSys<SYS>::template f_take<4 * J>(x, gst, qt);
+    if (slot == 0) return GroupSys<SYS>::template f_take<4 * J + 1>(x, gst, qt);
+    return GroupSys<SYS>::template f_take<4 * J + 2>(x, gst, qt);
 }
 
 template <int SYS> struct has_group { static constexpr bool value = false; };
@@ -505,57 +580,159 @@ __global__ void __launch_bounds__(64) rk_group_kernel(LaneArgs args, int n_slice
             }
         }
     };
-    // Lane batching (group_batch_slots above): fixed-step mode only, where the constant component's
-    // k is the same at every step -- h * (1 * sc), the step's own expressions -- and the per-lane
-    // offsets a*k of the batched stage inputs are set once, here.  (Linspace mode has another h at
-    // every step and keeps the unbatched form.)
-    constexpr bool BATCH = !LINSPACE && group_batches<GroupSys<SYS>, T>::value;
-    if constexpr (BATCH) {
-        double o = one;
-        if constexpr (NORM) o = one * sc;
-        const double kc = dt * o;
-        constexpr double a0 = group_batch_coef<T>(0), a1 = group_batch_coef<T>(1);
-        GroupSys<SYS>::batch_init(gst, tid % 16, a0 * kc, a1 * kc);
-    }
     // The tableau is folded (nngp_rk_dev.h, fold_*): k[j] holds k'_j = (a_j h) o_j, the one multiply
     // h o_j costs, and the stage inputs and the update take the rescaled coefficients (RK4:
-    // u + k'0, u + k'1, u + k2 and (1/3) k'0 + (2/3) k'1 + (1/3) k2 + (1/6) k3).  The batched
-    // offsets above stay a*RN(dt*o), the values the reference forms.  (Exact build only: the
-    // contracted build keeps stage_input and step_update, FOLD_TABLEAU in nngp_rk_dev.h.)
-    auto step = [&](int64_t n) __attribute__((always_inline)) {
-        const double h = LINSPACE ? grid.next(n, T0, T1, dt) : dt;
-#pragma unroll
-        for (int s = 0; s < S; s++) {
-            double tmp;
-            if constexpr (BATCH) tmp = s == 0 ? u + gst.OFF : fold_stage_input<T>(s, u, k);
-            else if constexpr (FOLD_TABLEAU) tmp = fold_stage_input<T>(s, u, k);
-            else tmp = stage_input<T, 1>(s, u, k, 0);
-            double o;
-            if constexpr (NORM) o = group_f<SYS, T, BATCH>(s, (tmp + 1) * hw + mn, gst, one, args) * sc;
-            else o = group_f<SYS, T, BATCH>(s, tmp, gst, one, args);
-            if constexpr (FOLD_TABLEAU) k[s] = fold_h<T>(s, h) * o;
-            else k[s] = h * o;
-        }
-        if constexpr (FOLD_TABLEAU) u = fold_step_update<T>(u, k);
-        else u = step_update<T, 1>(u, k, 0);
-    };
+    // u + k'0, u + k'1, u + k2 and (1/3) k'0 + (2/3) k'1 + (1/3) k2 + (1/6) k3).  (Exact build
+    // only: the contracted build keeps stage_input and step_update, FOLD_TABLEAU in nngp_rk_dev.h.)
     // UNROLL steps per iteration and a remainder loop: the step is one wave's instruction issue with
     // no other wave on the SIMD to cover the loop's taken branch.  Sixteen
     // for the tableaux of up to four stages (RK4: about 10 KB of loop body, inside the instruction
     // cache); RK8's eleven stay at two (code size).
     constexpr int UNROLL = S <= 4 ? 16 : 2;
-    int64_t n = 0;
-    for (; n + (UNROLL - 1) < steps; n += UNROLL) {
+    // The time track (group_tracks above): fixed-step mode only, where the constant component's k
+    // are the same at every step.  (Linspace mode has another h at every step and keeps the form
+    // below, as do the tableaux and the systems the track is not built for.)
+    constexpr bool TRACK = !LINSPACE && FOLD_TABLEAU && group_tracks<GroupSys<SYS>, T>::value;
+    if constexpr (TRACK) {
+        using GS = GroupSys<SYS>;
+        constexpr int TC = GS::TC;
+        static_assert(G == 16 && UNROLL % TRACK_STEPS == 0 && TC < D, "four lanes per step of a pass");
+        // Component TC's constants in every lane, and its k, INC and offsets from the step's own
+        // expressions: o = 1 * sc, k'_s = fold_h(s) * o, INC = their sum in fold_step_update's
+        // order, and the offsets a*RN(dt*o), the values the reference forms.
+        double mn2 = 0, hw2 = 0, o2 = one;
+        if constexpr (NORM) {
+            mn2 = args.norm[TC];
+            hw2 = 0.5 * args.norm[D + TC];
+            o2 = one * args.norm[2 * D + TC];
+        }
+        double kk[S];
 #pragma unroll
-        for (int j = 0; j < UNROLL; j++) {
-            step(n + j);
+        for (int s = 0; s < S; s++) kk[s] = fold_h<T>(s, dt) * o2;
+        double inc = fold_step_sum<T>(kk);
+        const double kc = dt * o2;
+        const int r = tid & 3;   // the lane's role; its step of the pass is c
+        double offr = r == 1 ? group_batch_coef<T>(0) * kc : r == 2 ? group_batch_coef<T>(1) * kc : -0.0;
+        double m1 = c >= 1 ? inc : -0.0, m2 = c >= 2 ? inc : -0.0, m3 = c >= 3 ? inc : -0.0;
+        // opaque from here on, so that every add of a per-lane constant stays one add: x + (-0.0) -> x
+        // is a legal fold that would move the add into the select
+        asm("" : "+v"(offr), "+v"(inc), "+v"(m1), "+v"(m2), "+v"(m3));
+        // tu: lane 4j + r holds u2 at step j of the pass, spread by the sequential roundings lane
+        // 4 TC performs on u
+        double tu = ((bcast<TC>(u) + m1) + m2) + m3;
+        // the pass's quotients from tu; tu advances by one of the pass's TRACK_STEPS steps
+        auto quot = [&]() __attribute__((always_inline)) {
+            double x = tu + offr;
+            if constexpr (NORM) x = (x + 1) * hw2 + mn2;
+            return GS::track_div(x, tu, inc, args);
+        };
+        auto advance = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 1; j < TRACK_STEPS; j++) tu = tu + inc;
+        };
+        // step J of the pass whose quotients qt holds
+        auto step = [&](auto J, double qt) __attribute__((always_inline)) {
+#pragma unroll
+            for (int s = 0; s < S; s++) {
+                const double tmp = fold_stage_input<T>(s, u, k);
+                double o;
+                if constexpr (NORM)
+                    o = group_f_track<SYS, T, decltype(J)::value>(s, (tmp + 1) * hw + mn, gst, qt) * sc;
+                else o = group_f_track<SYS, T, decltype(J)::value>(s, tmp, gst, qt);
+                k[s] = fold_h<T>(s, dt) * o;
+            }
+            u = fold_step_update<T>(u, k);
+            sample();
+        };
+        // One pass: the next pass's quotients are formed while this one's are used (they read
+        // nothing the steps write), so qt is always ready, for the remainder too.
+        double qt = quot();
+        advance();
+        GS::track_settle(gst);
+        // Inside a pass the second stage of its first steps is the doubly fused take stage
+        // (GroupSys<HOPF>::f_take2), which carries two instructions of the next pass's division
+        // each (pair K, from tu0 = the track at the start of the pass): three such stages in
+        // normalised coordinates, one in identity coordinates, as many as leave the track enough
+        // free instructions for the wait states behind the stage-0 statements.
+        typename GS::Tk tk{0.0, 0.0, 0.0};
+        auto step2 = [&](auto J, auto K, double qt, double tu0) __attribute__((always_inline)) {
+            constexpr int j = decltype(J)::value, kf = decltype(K)::value;
+            static_assert(group_batch_slot<T>(1) == 0, "stage 1 takes lane 4 j + 1");
+#pragma unroll
+            for (int s = 0; s < S; s++) {
+                const double tmp = fold_stage_input<T>(s, u, k);
+                double x = tmp;
+                if constexpr (NORM) x = (tmp + 1) * hw + mn;
+                double o;
+                if (s == 1) o = GS::template f_take2<4 * j + 1, kf>(x, gst, qt, tk, tu0, offr, hw2, mn2, args);
+                else o = group_f_track<SYS, T, j>(s, x, gst, qt);
+                if constexpr (NORM) o = o * sc;
+                k[s] = fold_h<T>(s, dt) * o;
+            }
+            u = fold_step_update<T>(u, k);
+            sample();
+        };
+        auto pass = [&]() __attribute__((always_inline)) {
+            const double tu0 = tu;
+            if constexpr (NORM) {
+                step2(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{}, qt, tu0);
+                step2(std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{}, qt, tu0);
+                step2(std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{}, qt, tu0);
+            } else {
+                step2(std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{}, qt, tu0);
+                tk.e = fma(-tk.q, args.param[0], tk.x);
+                step(std::integral_constant<int, 1>{}, qt);
+                step(std::integral_constant<int, 2>{}, qt);
+            }
+            const double next = GS::track_fin(tk, tu, inc, args);
+            advance();
+            step(std::integral_constant<int, 3>{}, qt);
+            qt = next;
+        };
+        static_assert(TRACK_STEPS == 4, "pass: four steps");
+        // (the long loop ends on n != full, a scalar compare: n + UNROLL - 1 < steps is a 64-bit
+        // signed one, which gfx950 has as a VALU op only)
+        const int64_t full = steps > 0 ? steps - steps % UNROLL : 0;
+        int64_t n = 0;
+        for (; n != full; n += UNROLL) {
+#pragma unroll
+            for (int j = 0; j < UNROLL / TRACK_STEPS; j++) pass();
+        }
+#pragma unroll 1
+        for (; n + (TRACK_STEPS - 1) < steps; n += TRACK_STEPS) pass();
+        if (n < steps) step(std::integral_constant<int, 0>{}, qt);
+        if (n + 1 < steps) step(std::integral_constant<int, 1>{}, qt);
+        if (n + 2 < steps) step(std::integral_constant<int, 2>{}, qt);
+    } else {
+        auto step = [&](int64_t n) __attribute__((always_inline)) {
+            const double h = LINSPACE ? grid.next(n, T0, T1, dt) : dt;
+#pragma unroll
+            for (int s = 0; s < S; s++) {
+                double tmp;
+                if constexpr (FOLD_TABLEAU) tmp = fold_stage_input<T>(s, u, k);
+                else tmp = stage_input<T, 1>(s, u, k, 0);
+                double o;
+                if constexpr (NORM) o = group_f<SYS, T>(s, (tmp + 1) * hw + mn, gst, one, args) * sc;
+                else o = group_f<SYS, T>(s, tmp, gst, one, args);
+                if constexpr (FOLD_TABLEAU) k[s] = fold_h<T>(s, h) * o;
+                else k[s] = h * o;
+            }
+            if constexpr (FOLD_TABLEAU) u = fold_step_update<T>(u, k);
+            else u = step_update<T, 1>(u, k, 0);
+        };
+        int64_t n = 0;
+        for (; n + (UNROLL - 1) < steps; n += UNROLL) {
+#pragma unroll
+            for (int j = 0; j < UNROLL; j++) {
+                step(n + j);
+                sample();
+            }
+        }
+#pragma unroll 1
+        for (; n < steps; n++) {
+            step(n);
             sample();
         }
-    }
-#pragma unroll 1
-    for (; n < steps; n++) {
-        step(n);
-        sample();
     }
     if constexpr (TRAJ) {
         if (writer) tr.last[c] = u;
