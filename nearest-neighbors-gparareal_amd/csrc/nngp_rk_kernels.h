@@ -88,6 +88,10 @@ __global__ void __launch_bounds__(64) rk_poly_lane_kernel(PolyLaneArgs args, int
 // issues anyway, and the sixteen-step loop ends on a scalar compare (69.75 VALU per step, round
 // 9: 71.06).  With the track's instructions as the fillers round 9 lacked, three stages per four
 // steps fuse the second subtraction of g as well (f_take2): 69.19 (profiles/r13/).
+// Since round 14 the sixteen-step loop in normalised coordinates is four asm statements, one per
+// pass of four steps, in an order of their own (GroupSys<HOPF>::pass_asm): the update's terms and
+// the track's instructions stand in the wait states of the fused ops, so fifteen of a pass's
+// sixteen stages fuse both subtractions, and no copy or `s_nop` is left: 66.0 (profiles/r14/).
 // Bitwise the lane kernel: each component is rounded by the same expression in the same order
 // (the fold: by an expression with the same real value at every rounding, for normal products).
 // ---------------------------------------------------------------------------------------------
@@ -329,6 +333,137 @@ template <> struct GroupSys<NNGP_SYS_HOPF> {     // systems.py:148-154, as LaneS
             : [e] "v"(tk.e), [q] "v"(tk.q), [r] "v"(a.rparam0), [inc] "v"(inc));
         return o;
     }
+    // A whole pass of the time track -- four RK4 steps in normalised coordinates, the next pass's
+    // quotients and the track's four adds -- as ONE asm statement (the sixteen-step loop of
+    // rk_group_kernel).  The compiler cannot see which
+    // instruction of an asm statement wrote an output, so it puts a wait state in front of
+    // whatever reads one next and fills it with the update's terms; with a statement per RHS those
+    // terms were spent on its padding.  Inside one statement nothing is inserted and the order is
+    // ours, so the update's terms and the track's instructions stand in the two slots F1 and F2
+    // of the doubly fused stage (f_take2's order), and fifteen of the sixteen stages of a pass
+    // subtract both squares by `v_fmac_f64_dpp`.  Every value is rounded by the expression the
+    // C++ form rounds it by, in the same order: x = ((u + k') + 1) hw + mn, the take stage,
+    // o sc, (a h) o, and u + (((b0 k'0 + b1 k'1) + b2 k2) + b3 k3) (fold_step_update).
+    // Fillers, per step j of the pass (T1..T7: + OFFr, + 1, hw2, + mn2, x r, the residual, the
+    // quotient; TA: tu + INC):
+    //   stage 0:  two of the track's      j = 0: T1 T2,  1: T4 T5,  2: T7 TA,  3: TA TA
+    //   stage 1:  b0 k'0, one of the track's      0: T3,     1: T6,     2: TA,     3: none
+    //   stage 2:  b1 k'1, the sum of the two
+    //   stage 3:  b2 k2, the next sum
+    // The track has eleven instructions for twelve slots, so stage 1 of step 3 keeps the singly
+    // fused form (f_take's: u1^2 through B2 and an add), which needs no filler: 4 x 63 + 1 + 11 =
+    // 264 VALU per pass.
+    // Wait states (every VGPR a DPP op reads written at least two instructions earlier), stage by
+    // stage as in f_take2: x -> (x x, Q) -> P; sq -> (Q, P, F1) -> fused; Q -> (P, F1) -> fused ->
+    // (P, F2) -> fused; P -> (F1, fused) -> P, and in the singly fused stage sq -> (Q, P) -> B2,
+    // Q -> (P, B2) -> fused, P -> (B2, fused) -> P.  No filler writes a register a DPP op reads
+    // but T7, the next pass's quotients QN: never the register this pass takes from (QT; the two
+    // alternate between consecutive passes through the operand bindings, so no copy is issued),
+    // and written in stage 0 of step 2, a step and a half before the statement ends.  From one
+    // stage to the next, Q, P and B2 are read no sooner than four plain ops after the stage's last
+    // fused op (x Q, the fma, sc, (a h), then the next stage's input).  Pass -> next pass, the
+    // loop's back edge included: the statement ends with the update's three plain ops and starts
+    // with x's three and x x, so its first DPP op is seven instructions from any write of the
+    // statement before, whatever the compiler puts between the two.
+    struct PassC {   // what a pass reads and does not write
+        double hw, mn, sc, h[4], b[4], inc, offr, hw2, mn2, r, mu;   // r, mu: div_const's 1/mu and mu
+    };
+#define NNGP_HOPF_T1 "v_add_f64 %[tx], %[tu], %[offr]"
+#define NNGP_HOPF_T2 "v_add_f64 %[tx], %[tx], 1.0"
+#define NNGP_HOPF_T3 "v_mul_f64 %[tx], %[tx], %[hw2]"
+#define NNGP_HOPF_T4 "v_add_f64 %[tx], %[tx], %[mn2]"
+#define NNGP_HOPF_T5 "v_mul_f64 %[tq], %[tx], %[r]"
+#define NNGP_HOPF_T6 "v_fma_f64 %[te], -%[tq], %[b], %[tx]"
+#define NNGP_HOPF_T7 "v_fma_f64 %[QN], %[te], %[r], %[tq]"
+#define NNGP_HOPF_TA "v_add_f64 %[tu], %[tu], %[inc]"
+#define NNGP_HOPF_U1 "v_mul_f64 %[a0], %[b0], %[k0]"
+#define NNGP_HOPF_U2 "v_mul_f64 %[a1], %[b1], %[k1]"
+#define NNGP_HOPF_U3 "v_add_f64 %[a0], %[a0], %[a1]"
+#define NNGP_HOPF_U4 "v_mul_f64 %[a1], %[b2], %[k2]"
+#define NNGP_HOPF_U5 "v_add_f64 %[a0], %[a0], %[a1]"
+    // the stage's input, de-normalised: stage 0 from u, a later stage from u + k' of the stage before
+#define NNGP_HOPF_IN0 "v_add_f64 %[x], %[u], 1.0\n\t"
+#define NNGP_HOPF_IN(K) "v_add_f64 %[x], %[u], %[" K "]\n\tv_add_f64 %[x], %[x], 1.0\n\t"
+    // x, the take stage with both subtractions fused (lane L of QT), then k'_s = (a h)(o sc) into K
+#define NNGP_HOPF_STAGE2(L, F1, F2, K, H)                                                \
+    "v_mul_f64 %[x], %[x], %[hw]\n\t"                                                    \
+    "v_add_f64 %[x], %[x], %[mn]\n\t"                                                    \
+    "v_mul_f64 %[sq], %[x], %[x]\n\t"                                                    \
+    "v_mov_b64_dpp %[Q], %[QT] row_newbcast:" L " row_mask:0xf bank_mask:0x3\n\t"        \
+    "v_mov_b64_dpp %[P], %[x] row_newbcast:4 row_mask:0xf bank_mask:0x1\n\t"             \
+    F1 "\n\t"                                                                            \
+    "v_fmac_f64_dpp %[Q], %[sq], %[M] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"     \
+    "v_mov_b64_dpp %[P], %[x] row_newbcast:0 row_mask:0xf bank_mask:0x2\n\t"             \
+    F2 "\n\t"                                                                            \
+    "v_fmac_f64_dpp %[Q], %[sq], %[M] row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"     \
+    "v_mul_f64 %[t], %[x], %[Q]\n\t"                                                     \
+    "v_fma_f64 %[t], %[S], %[P], %[t]\n\t"                                               \
+    "v_mul_f64 %[t], %[t], %[sc]\n\t"                                                    \
+    "v_mul_f64 %[" K "], %[" H "], %[t]\n\t"
+    // the same with f_take's singly fused stage, which has no slot to fill
+#define NNGP_HOPF_STAGE1(L, K, H)                                                        \
+    "v_mul_f64 %[x], %[x], %[hw]\n\t"                                                    \
+    "v_add_f64 %[x], %[x], %[mn]\n\t"                                                    \
+    "v_mul_f64 %[sq], %[x], %[x]\n\t"                                                    \
+    "v_mov_b64_dpp %[Q], %[QT] row_newbcast:" L " row_mask:0xf bank_mask:0x3\n\t"        \
+    "v_mov_b64_dpp %[P], %[x] row_newbcast:4 row_mask:0xf bank_mask:0x1\n\t"             \
+    "v_mov_b64_dpp %[B2], %[sq] row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"           \
+    "v_fmac_f64_dpp %[Q], %[sq], %[M] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"     \
+    "v_mov_b64_dpp %[P], %[x] row_newbcast:0 row_mask:0xf bank_mask:0x2\n\t"             \
+    "v_add_f64 %[t], %[Q], -%[B2]\n\t"                                                   \
+    "v_mul_f64 %[t], %[x], %[t]\n\t"                                                     \
+    "v_fma_f64 %[t], %[S], %[P], %[t]\n\t"                                               \
+    "v_mul_f64 %[t], %[t], %[sc]\n\t"                                                    \
+    "v_mul_f64 %[" K "], %[" H "], %[t]\n\t"
+    // stages 2 and 3 and the end of the update, the same in every step; L1, L3: the lanes of the
+    // quotients of stages 1 and 2, and of stage 3
+#define NNGP_HOPF_STEP_END(L1, L3)                                                       \
+    NNGP_HOPF_IN("k1") NNGP_HOPF_STAGE2(L1, NNGP_HOPF_U2, NNGP_HOPF_U3, "k2", "h2")      \
+    NNGP_HOPF_IN("k2") NNGP_HOPF_STAGE2(L3, NNGP_HOPF_U4, NNGP_HOPF_U5, "k3", "h3")      \
+    "v_mul_f64 %[a1], %[b3], %[k3]\n\t"                                                  \
+    "v_add_f64 %[a0], %[a0], %[a1]\n\t"                                                  \
+    "v_add_f64 %[u], %[u], %[a0]\n\t"
+    // a step whose stages 0 and 1 carry the track's TA, TB and TC
+#define NNGP_HOPF_STEP(L0, L1, L3, TA_, TB_, TC_)                                        \
+    NNGP_HOPF_IN0 NNGP_HOPF_STAGE2(L0, TA_, TB_, "k0", "h0")                             \
+    NNGP_HOPF_IN("k0") NNGP_HOPF_STAGE2(L1, NNGP_HOPF_U1, TC_, "k1", "h1")               \
+    NNGP_HOPF_STEP_END(L1, L3)
+    __device__ static void pass_asm(double &u, St &s, double qt, double &qn, double &tu, const PassC &c) {
+        double x, sq, t, k0, k1, k2, k3, a0, a1, tx, tq, te;
+        asm(NNGP_HOPF_STEP("0", "1", "2", NNGP_HOPF_T1, NNGP_HOPF_T2, NNGP_HOPF_T3)
+            NNGP_HOPF_STEP("4", "5", "6", NNGP_HOPF_T4, NNGP_HOPF_T5, NNGP_HOPF_T6)
+            NNGP_HOPF_STEP("8", "9", "10", NNGP_HOPF_T7, NNGP_HOPF_TA, NNGP_HOPF_TA)
+            NNGP_HOPF_IN0 NNGP_HOPF_STAGE2("12", NNGP_HOPF_TA, NNGP_HOPF_TA, "k0", "h0")
+            NNGP_HOPF_U1 "\n\t"
+            NNGP_HOPF_IN("k0") NNGP_HOPF_STAGE1("13", "k1", "h1")
+            NNGP_HOPF_STEP_END("13", "14")
+            : [u] "+v"(u), [tu] "+v"(tu), [Q] "+v"(s.Q), [P] "+v"(s.P), [B2] "+v"(s.B2), [QN] "=&v"(qn),
+              [x] "=&v"(x), [sq] "=&v"(sq), [t] "=&v"(t), [k0] "=&v"(k0), [k1] "=&v"(k1), [k2] "=&v"(k2),
+              [k3] "=&v"(k3), [a0] "=&v"(a0), [a1] "=&v"(a1), [tx] "=&v"(tx), [tq] "=&v"(tq), [te] "=&v"(te)
+            : [QT] "v"(qt), [S] "v"(s.S), [M] "v"(s.M), [hw] "v"(c.hw), [mn] "v"(c.mn), [sc] "v"(c.sc),
+              [h0] "v"(c.h[0]), [h1] "v"(c.h[1]), [h2] "v"(c.h[2]), [h3] "v"(c.h[3]), [b0] "v"(c.b[0]),
+              [b1] "v"(c.b[1]), [b2] "v"(c.b[2]), [b3] "v"(c.b[3]), [inc] "v"(c.inc), [offr] "v"(c.offr),
+              [hw2] "v"(c.hw2), [mn2] "v"(c.mn2), [r] "v"(c.r), [b] "v"(c.mu));
+    }
+#undef NNGP_HOPF_STEP
+#undef NNGP_HOPF_STEP_END
+#undef NNGP_HOPF_STAGE1
+#undef NNGP_HOPF_STAGE2
+#undef NNGP_HOPF_IN
+#undef NNGP_HOPF_IN0
+#undef NNGP_HOPF_U5
+#undef NNGP_HOPF_U4
+#undef NNGP_HOPF_U3
+#undef NNGP_HOPF_U2
+#undef NNGP_HOPF_U1
+#undef NNGP_HOPF_TA
+#undef NNGP_HOPF_T7
+#undef NNGP_HOPF_T6
+#undef NNGP_HOPF_T5
+#undef NNGP_HOPF_T4
+#undef NNGP_HOPF_T3
+#undef NNGP_HOPF_T2
+#undef NNGP_HOPF_T1
 #undef NNGP_HOPF_TAKE2
 #undef NNGP_HOPF_HEAD
 #undef NNGP_HOPF_TAIL
@@ -694,9 +829,33 @@ __global__ void __launch_bounds__(64) rk_group_kernel(LaneArgs args, int n_slice
         // signed one, which gfx950 has as a VALU op only)
         const int64_t full = steps > 0 ? steps - steps % UNROLL : 0;
         int64_t n = 0;
-        for (; n != full; n += UNROLL) {
+        if constexpr (NORM && !TRAJ) {
+            // The long loop in normalised coordinates: each pass is one asm statement in an order
+            // of its own (GroupSys<HOPF>::pass_asm), fifteen of its sixteen stages doubly fused.
+            // The quotients alternate between two registers, so a pass writes the one the next
+            // reads without a copy; an iteration holds an even number of passes and ends on qt.
+            static_assert(S == 4 && (UNROLL / TRACK_STEPS) % 2 == 0, "pass_asm: RK4, passes in pairs");
+            typename GS::PassC pc{hw, mn, sc,
+                                  {fold_h<T>(0, dt), fold_h<T>(1, dt), fold_h<T>(2, dt), fold_h<T>(3, dt)},
+                                  {fold_b<T>(0), fold_b<T>(1), fold_b<T>(2), fold_b<T>(3)},
+                                  inc, offr, hw2, mn2, args.rparam0, args.param[0]};
+            // the wave-uniform ones in VGPRs once, in front of the loop: left to itself the
+            // compiler moves them there from their SGPRs again in every iteration
+            asm("" : "+v"(pc.b[0]), "+v"(pc.b[1]), "+v"(pc.b[2]), "+v"(pc.b[3]), "+v"(pc.hw2), "+v"(pc.mn2),
+                     "+v"(pc.r), "+v"(pc.mu));
+            double qo;
+            for (; n != full; n += UNROLL) {
 #pragma unroll
-            for (int j = 0; j < UNROLL / TRACK_STEPS; j++) pass();
+                for (int j = 0; j < UNROLL / TRACK_STEPS / 2; j++) {
+                    GS::pass_asm(u, gst, qt, qo, tu, pc);
+                    GS::pass_asm(u, gst, qo, qt, tu, pc);
+                }
+            }
+        } else {
+            for (; n != full; n += UNROLL) {
+#pragma unroll
+                for (int j = 0; j < UNROLL / TRACK_STEPS; j++) pass();
+            }
         }
 #pragma unroll 1
         for (; n + (TRACK_STEPS - 1) < steps; n += TRACK_STEPS) pass();
