@@ -1,8 +1,8 @@
 """NumPy restatement of the ELM arithmetic contract: the random-weights feature
 map in the summation order of csrc/nngp_elm.hip (elm_hidden_kernel), the Gram-Schmidt solve of
 elm_solve_kernel, and a Parareal loop with this model on the oracle's propagators and kNN.  It is
-the bitwise yardstick of tests/test_gpu_elm.py, itself checked on the CPU against the reference's
-ELM_base (tests/test_elm_host.py, tests/golden/elm.npz).  NumPy's elementwise fp64 add / sub / mul
+the bitwise yardstick of tests/test_gpu_elm.py and tests/test_gpu_elm_forms.py, itself checked on the
+CPU against the reference's ELM_base (tests/test_elm_host.py, tests/golden/elm.npz, elm_wide.npz).  NumPy's elementwise fp64 add / sub / mul
 / div / sqrt are IEEE, one rounding per operation, so this is bit-reproducible.  Not a test module
 (no test_ prefix)."""
 import os

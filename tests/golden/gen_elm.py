@@ -1,9 +1,15 @@
-"""Generate tests/golden/elm.npz by running the REFERENCE's ELM model itself.
+"""Generate tests/golden/elm.npz and tests/golden/elm_wide.npz by running the REFERENCE's ELM model
+itself.
 
 Development container only, like gen_diffreact.py (the reference tree and this script never travel
-to the GPU box; only the .npz is committed):
+to the GPU box; only the .npz files are committed):
 
-    PYTHONPATH=tests/golden/jaxshim:<reference tree> python tests/golden/gen_elm.py
+    PYTHONPATH=tests/golden/jaxshim:<reference tree> python tests/golden/gen_elm.py          # elm.npz
+    PYTHONPATH=tests/golden/jaxshim:<reference tree> python tests/golden/gen_elm.py wide     # elm_wide.npz
+
+Each invocation writes one fixture and leaves the other alone.  elm_wide.npz holds predictions only,
+at wide hidden layers: the reference's default res_size = 500 at degree 2, and two degree-1 sets, one
+with more hidden units than m - 1 can use up (200) and one nearer to it (100), at m up to 16.
 
 Every number written is computed by reference code (models.py:476-554 ELM_base / ELM, parareal.py,
 solver.py, systems.py) or, for the recorded condition numbers, by numpy on the reference's own
@@ -27,6 +33,9 @@ warnings.filterwarnings('ignore')   # Ridge(alpha=0) on a singular centred Gram 
 WEIGHTS = ((2, 20, 2), (3, 20, 2), (3, 7, 1), (16, 50, 2))   # (d, res_size, degree)
 MS = (1, 2, 4, 7)
 N_CASES, N_TRAIN = 10, 20
+WIDE_WEIGHTS = ((3, 500, 2), (16, 200, 1), (3, 100, 1))   # elm_wide.npz
+WIDE_MS = (5, 10, 16)
+WIDE_N_TRAIN = 40
 
 
 def gram_cond(mdl, xm):
@@ -40,15 +49,15 @@ def gram_cond(mdl, xm):
     return float(ev[0] / ev[-1]) if ev[-1] > 0 else np.inf
 
 
-def part_predict(arrs):
-    for d, res, deg in WEIGHTS:
+def part_predict(arrs, weights=WEIGHTS, ms=MS, n_train=N_TRAIN, seed0=1000):
+    for d, res, deg in weights:
         tag = f'w__{d}_{res}_{deg}'
-        rng = np.random.default_rng(1000 + 10 * d + deg)
-        X = rng.uniform(-1, 1, (N_CASES, N_TRAIN, d))
-        Y = rng.uniform(-1, 1, (N_CASES, N_TRAIN, d))
+        rng = np.random.default_rng(seed0 + 10 * d + deg)
+        X = rng.uniform(-1, 1, (N_CASES, n_train, d))
+        Y = rng.uniform(-1, 1, (N_CASES, n_train, d))
         Q = rng.uniform(-1, 1, (N_CASES, d))
         arrs[tag + '__X'], arrs[tag + '__Y'], arrs[tag + '__Q'] = X, Y, Q
-        for m in MS:
+        for m in ms:
             mdl = rmodels.ELM_base(d=d, seed=47, res_size=res, degree=deg, m=m)
             arrs[tag + '__bias'], arrs[tag + '__C'] = mdl.bias, mdl.C
             preds, conds = [], []
@@ -80,12 +89,21 @@ def part_runs(arrs):
                 arrs[tag + '__u'] = np.asarray(res['u'])[:, :, :3]
 
 
+def part_predict_wide(arrs):
+    """The same quantities as part_predict at the wide weight sets (seeds 2000 + 10 d + degree)."""
+    part_predict(arrs, WIDE_WEIGHTS, WIDE_MS, WIDE_N_TRAIN, 2000)
+
+
 if __name__ == '__main__':
+    import sys
+    wide = sys.argv[1:] == ['wide']
+    if sys.argv[1:] and not wide:
+        raise SystemExit('usage: gen_elm.py [wide]')
     arrs = {}
-    for part in (part_predict, part_runs):
+    for part in ((part_predict_wide,) if wide else (part_predict, part_runs)):
         st = time.time()
         part(arrs)
         print(part.__name__, f'{time.time() - st:.1f}s', flush=True)
-    path = os.path.join(HERE, 'elm.npz')
+    path = os.path.join(HERE, 'elm_wide.npz' if wide else 'elm.npz')
     np.savez_compressed(path, **arrs)
     print('wrote', path, os.path.getsize(path), 'bytes', flush=True)

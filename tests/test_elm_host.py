@@ -1,5 +1,5 @@
 """CPU: the ELM arithmetic contract's NumPy restatement (tests/elm_ref.py) against the reference's
-own ELM_base (tests/golden/elm.npz, written by tests/golden/gen_elm.py), and the ELM surface's
+own ELM_base (tests/golden/elm.npz and elm_wide.npz, written by tests/golden/gen_elm.py), and the ELM surface's
 refusals and argument checks, none of which needs a GPU.
 
 Tolerances.  The restatement is a min-norm solve on differences, the reference a
@@ -12,6 +12,9 @@ wherever it drops no further row, and differs from the reference by O(1) where i
 150 well-conditioned fixture cases; the first correction of both whole runs).
 Measured with the restatement at TAU_EXACT on the development CPU, relative to max(1, |ref|):
   predictions, fixture cases with cond <= 1e6 (150 of 160):   9.49e-13   -> bound 100 x = 9.49e-11
+  wide layers (tests/golden/elm_wide.npz: res_size 500 at degree 2, 200 and 100 at degree 1, m = 5, 10,
+  16, 40 training rows), cond <= 1e6 (90 of 90, largest 3.4e4): 8.63e-13   -> bound 100 x = 8.63e-11
+  (the model's TAU drops a further neighbour in 13 of those 90)
   whole run, column 1 (the first correction), Lorenz N = 32:  2.96e-10   -> bound 100 x = 2.96e-8
   whole run, column 1, FHN-ODE N = 40:                        2.74e-12   -> bound 100 x = 2.74e-10
 The factor 100 covers BLAS / sklearn builds that order their sums differently; the GPU gets no
@@ -30,6 +33,9 @@ WEIGHTS = ((2, 20, 2), (3, 20, 2), (3, 7, 1), (16, 50, 2))   # (d, res_size, deg
 MS = (1, 2, 4, 7)
 COND_MAX = 1e6
 PRED_MEASURED, PRED_BOUND = 9.49e-13, 100 * 9.49e-13
+WIDE_WEIGHTS = ((3, 500, 2), (16, 200, 1), (3, 100, 1))   # of tests/golden/elm_wide.npz
+WIDE_MS = (5, 10, 16)
+WIDE_MEASURED, WIDE_BOUND = 8.63e-13, 100 * 8.63e-13
 COL1 = {'lorenz': (2.96e-10, 100 * 2.96e-10), 'fhn_ode': (2.74e-12, 100 * 2.74e-12)}   # measured, bound
 
 
@@ -49,13 +55,14 @@ def test_feature_order_is_sklearns():
     assert E.feature_pairs(3) == [(0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)]
 
 
-def test_predictions_agree_with_the_reference_where_it_is_well_conditioned():
-    z = golden('elm.npz')
+def _compare_predictions(z, weights, ms):
+    """(largest relative difference at TAU_EXACT, cases compared, cases in all, cases where the model's
+    TAU drops a further neighbour) over the fixture z; asserts the model-threshold property."""
     worst, under, total, dropped = 0.0, 0, 0, 0
-    for d, res, deg in WEIGHTS:
+    for d, res, deg in weights:
         tag = f'w__{d}_{res}_{deg}'
         X, Y, Q = z[tag + '__X'], z[tag + '__Y'], z[tag + '__Q']
-        for m in MS:
+        for m in ms:
             ref, cond = z[tag + f'__pred_m{m}'], z[tag + f'__cond_m{m}']
             for c in range(X.shape[0]):
                 total += 1
@@ -75,10 +82,36 @@ def test_predictions_agree_with_the_reference_where_it_is_well_conditioned():
                     assert np.array_equal(pred, exact)
                 else:
                     dropped += 1
+    return worst, under, total, dropped
+
+
+def test_predictions_agree_with_the_reference_where_it_is_well_conditioned():
+    worst, under, total, dropped = _compare_predictions(golden('elm.npz'), WEIGHTS, MS)
     print(f'largest relative difference {worst:.3e} over {under} of {total} cases (measured {PRED_MEASURED:.3e}); '
           f'TAU = 2^-8 drops a further neighbour in {dropped} of them')
     assert under >= 0.9 * total, (under, total)   # the cap must not hide a failure
     assert worst <= PRED_BOUND, worst
+
+
+@pytest.mark.parametrize('d,res,deg', WIDE_WEIGHTS)
+def test_wide_weights_equal_the_reference_bitwise(d, res, deg):
+    z = golden('elm_wide.npz')
+    tag = f'w__{d}_{res}_{deg}'
+    bias, C = E.draw_weights(d, 47, res, deg)
+    assert C.shape == (res, E.n_poly(d, deg))
+    assert np.array_equal(bias, z[tag + '__bias'][:, 0]) and np.array_equal(C, z[tag + '__C'])
+
+
+def test_wide_predictions_agree_with_the_reference_where_it_is_well_conditioned():
+    """The restatement at the reference's default width (res_size = 500) and at degree 1 with m up to 16:
+    every dot product over res_size longer than a wave, 40 training rows."""
+    z = golden('elm_wide.npz')
+    assert z['w__3_500_2__X'].shape == (10, 40, 3) and z['w__16_200_1__pred_m16'].shape == (10, 16)
+    worst, under, total, dropped = _compare_predictions(z, WIDE_WEIGHTS, WIDE_MS)
+    print(f'wide: largest relative difference {worst:.3e} over {under} of {total} cases (measured '
+          f'{WIDE_MEASURED:.3e}); TAU = 2^-8 drops a further neighbour in {dropped} of them')
+    assert total == 90 and under >= 0.9 * total, (under, total)   # the cap must not hide a failure
+    assert worst <= WIDE_BOUND, worst
 
 
 @pytest.mark.parametrize('name', sorted(RUNS))
