@@ -4,7 +4,11 @@
 // branches on comparisons of those values, so a single last-ulp difference between two libms
 // (ocml on the GPU, glibc in the CPU oracle) redirects whole fits.  These routines are plain
 // IEEE arithmetic + fma + ldexp + rint, all exactly specified, so the GPU and the oracle's copy
-// (oracle/nngp_oracle.c, same algorithm and constants) agree bit for bit.  Accuracy ~1 ulp.
+// (oracle/nngp_oracle.c, same algorithm and constants) agree bit for bit -- checked directly, routine
+// by routine, at thresholds, subnormal results, reduction ties and special values
+// (tests/test_gpu_math_probe.py through tests/probe/nngp_math_probe.hip).  True error, measured
+// against 200-bit mpmath (tests/test_oracle_golden.py::test_math_true_error, asserted <= 1 ulp):
+// exp 0.81 ulp (0.80 where the result is subnormal, in ulps of 2^-1074), 10^x 0.93, log 0.62.
 //   exp:  Cody-Waite reduction x = n ln2 + r (|r| <= ln2/2), degree-13 Taylor (Horner, fma)
 //   10^x: the same with the argument x*ln10 carried as a double-double
 //   log:  fdlibm __ieee754_log (Sun Microsystems, freely distributable): x = 2^k (1+f),
@@ -90,7 +94,8 @@ __device__ __forceinline__ double nn_exp(double x) { return nn_exp_t<false>(x, 0
 __device__ __forceinline__ double nn_exp_nonpos(double x) { return nn_exp_t<true>(x, 0.0); }
 __device__ __forceinline__ double nn_exp_nonpos_sep(double x) { return nn_exp_t<true, false>(x, 0.0); }
 
-// sqrt(x) and 1.0/x, correctly rounded, for x in [2^-500, 2^500]: the instruction sequences the
+// sqrt(x) and 1.0/x, correctly rounded, for x in [2^-500, 2^500 (1 + 2^-20)), the set in_mid_range
+// accepts (verified against IEEE on the hardware, tests/test_gpu_math_probe.py): the sequences the
 // compiler emits for sqrt() and 1.0/x on gfx950 (rsq + Goldschmidt with two corrections; rcp +
 // two Newton steps + the Markstein quotient correction) without the range scaling (ldexp /
 // v_div_scale) and special-value fixups (v_cmp_class / v_div_fixup), which are identities on that
@@ -113,10 +118,33 @@ __device__ __forceinline__ double rcp_mid(double b) {
     y = fma(y, fma(-b, y, 1.0), y);
     return fma(fma(-b, y, 1.0), y, y);   // q = 1*y; r = 1 - b q; q + r y
 }
-// x in [2^-500, 2^500] (NaN and negatives excluded): one compare on the high word
+// 2^-500 <= x < 2^500 (1 + 2^-20) (NaN, zeros, negatives and infinities excluded): one unsigned
+// compare on the high word, which drops the low 32 mantissa bits -- so the upper end is the first
+// double whose high word passes 2^500's, not 2^500 itself.  sqrt_mid / rcp_mid hold on the whole
+// accepted set (tests/test_gpu_math_probe.py checks them there, against the device's own sqrt and
+// division and against IEEE).
 __device__ __forceinline__ bool in_mid_range(double x) {
     const unsigned hi = (unsigned)(__double_as_longlong(x) >> 32);
     return hi - 0x20B00000u <= 0x5F300000u - 0x20B00000u;
+}
+
+// ljj = sqrt(x), ri = 1.0/ljj, both correctly rounded, for every x > 0 (the lanes kernels' pivots
+// that pass, nngp_nmlane.hip; tests/test_gpu_math_probe.py checks it from 2^-1074 to DBL_MAX):
+// the short mid-range sequences (sqrt_mid / rcp_mid above, exact on [2^-500, 2^500]) on x
+// scaled by 4^k, k in {300, 0, -300}, and the results scaled back by 2^-k / 2^k -- exact, since
+// sqrt(x 4^k) = sqrt(x) 2^k and both results stay normal (sqrt(x) in [2^-537, 2^512]).  x = +inf
+// gives (inf, 0) as sqrt / division do.  Branch-free: a uniform branch to the full sequences was
+// if-converted by LLVM, which then ran both (and held both's registers) at every column.
+__device__ __forceinline__ void sqrt_rcp_exact(double x, double &ljj, double &ri) {
+    const int k = x < 0x1p-500 ? 300 : (x > 0x1p+500 ? -300 : 0);
+    const double s = sqrt_mid(ldexp(x, 2 * k));
+    const double r = rcp_mid(s);
+    // +inf -> (inf, 0) by bit masks, not a select: LLVM turned the select into a branch around the
+    // whole sequence (a divergent branch per column, values spilled across it)
+    const long long m = -(long long)(x == __builtin_huge_val());   // all ones for +inf
+    const long long ls = __double_as_longlong(ldexp(s, -k)), lr = __double_as_longlong(ldexp(r, k));
+    ljj = __longlong_as_double((ls & ~m) | (0x7FF0000000000000ll & m));
+    ri = __longlong_as_double(lr & ~m);
 }
 
 // 10^x = exp(x ln10), x ln10 as a double-double (models.py: 10**sigma)
@@ -159,7 +187,12 @@ __device__ __forceinline__ double nn_log(double x_in) {
 // :182-189), fully specified like exp/log above so the GPU and the oracle agree bit for bit:
 // x = n pi/2 + r by a three-term fma Cody-Waite reduction (fdlibm's 33-bit pi/2 pieces; exact
 // n*PIO2_1 for |n| < 2^20), then fdlibm's __kernel_sin / __kernel_cos polynomials on |r| <= pi/4
-// and the quadrant select.  ~1 ulp for the |x| < 1e5 these fields see.
+// and the quadrant select.  True error (200-bit mpmath, tests/test_oracle_golden.py::
+// test_math_true_error): |result - true| <= 2 max(ulp(true), 2^-62) on |x| <= 1e4 (measured: sin 1.78,
+// cos 1.58), and 2.23 / 1.96 on the |x| <= 1e5 these fields see.  The bound is an absolute one with a
+// floor, not a relative one: next to a multiple of pi the reduction leaves ~1e-26, many ulps of a tiny
+// true value -- at x = RN(29 pi) = -91.106186954104 the sine, 5.3e-15, is off by 5e-27, 2.6e4 ulp of
+// itself and nothing for a vector field.
 struct TrigC {
     static constexpr double INVPIO2 = 6.36619772367581382433e-01;
     static constexpr double PIO2_1 = 1.57079632673412561417e+00;
@@ -220,7 +253,8 @@ __device__ __forceinline__ void nn_sincos(double x, double &sn, double &cs) {
 // field's whole attractor range |x| <= b/a = 20 with margin, 2e5 points on |x| <= 25; |x| <= 1e4).
 // Range of validity: the parity trick needs |n| < 2^51, i.e. |x| < pi*2^51; the three-term
 // reduction keeps the 2-ulp bound only while n*PI_3's rounding stays far below r's ulp (measured
-// to |x| = 1e4; ThomasLabyrinth's states stay within |x| <= 20).
+// to |x| = 1e4; ThomasLabyrinth's states stay within |x| <= 20).  True error, with nn_sincos's floor:
+// 1.35 ulp on |x| <= 25, 1.78 on |x| <= 1e4 (asserted <= 2).
 struct SinPiC {
     static constexpr double INVPI = 0x1.45f306dc9c883p-2;
     static constexpr double PI_1 = 2 * 1.57079632673412561417e+00, PI_2 = 2 * 6.07710050630396597660e-11,

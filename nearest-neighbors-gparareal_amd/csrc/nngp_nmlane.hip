@@ -108,23 +108,7 @@ __device__ __forceinline__ double mk_div(double x, double lii, double ri) {
     return fma(fma(-q, lii, x), ri, q);
 }
 
-// ljj = sqrt(x), ri = 1.0/ljj, both correctly rounded, for every x > 0 (the pivots that pass):
-// the short mid-range sequences (nngp_math.h sqrt_mid / rcp_mid, exact on [2^-500, 2^500]) on x
-// scaled by 4^k, k in {300, 0, -300}, and the results scaled back by 2^-k / 2^k -- exact, since
-// sqrt(x 4^k) = sqrt(x) 2^k and both results stay normal (sqrt(x) in [2^-537, 2^512]).  x = +inf
-// gives (inf, 0) as sqrt / division do.  Branch-free: a uniform branch to the full sequences was
-// if-converted by LLVM, which then ran both (and held both's registers) at every column.
-__device__ __forceinline__ void sqrt_rcp_exact(double x, double &ljj, double &ri) {
-    const int k = x < 0x1p-500 ? 300 : (x > 0x1p+500 ? -300 : 0);
-    const double s = sqrt_mid(ldexp(x, 2 * k));
-    const double r = rcp_mid(s);
-    // +inf -> (inf, 0) by bit masks, not a select: LLVM turned the select into a branch around the
-    // whole sequence (a divergent branch per column, values spilled across it)
-    const long long m = -(long long)(x == __builtin_huge_val());   // all ones for +inf
-    const long long ls = __double_as_longlong(ldexp(s, -k)), lr = __double_as_longlong(ldexp(r, k));
-    ljj = __longlong_as_double((ls & ~m) | (0x7FF0000000000000ll & m));
-    ri = __longlong_as_double(lr & ~m);
-}
+// (sqrt_rcp_exact, the pivot's sqrt and reciprocal for every x > 0: nngp_math.h)
 
 // oracle butterfly_sum over the fit's rows r < M of v[r] (row r = LPF s + q in slot s of lane q):
 // fold rows >= 16 into rows r mod 16 (adding the oracle's 0.0 for missing ones), then levels

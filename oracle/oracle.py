@@ -82,6 +82,10 @@ def lib():
         L.orc_solves.argtypes = [i32, _dp, _dp, _dp, _dp]
         L.orc_exp_array.argtypes = [i64, _dp, _dp]
         L.orc_log_array.argtypes = [i64, _dp, _dp]
+        L.orc_exp_dd_array.argtypes = [i64, _dp, _dp, _dp]
+        L.orc_pow10_array.argtypes = [i64, _dp, _dp]
+        L.orc_sincos_array.argtypes = [i64, _dp, _dp, _dp]
+        L.orc_sin_pi_array.argtypes = [i64, _dp, _dp]
         for fn in ('nn_exp', 'nn_log', 'nn_pow10', 'nn_sin', 'nn_cos', 'nn_sin_pi'):
             getattr(L, fn).argtypes = [dbl]
             getattr(L, fn).restype = dbl

@@ -6,7 +6,8 @@ run_nm_parked, run_nm_lanes) that says which kernel template a call reaches.
 
 The fits run padded to one of 8 sizes (maxm_for) and the arithmetic order of one evaluation depends
 on the exact m (dpotf2's (m-1-j) & 3 tail rows, the lane pairing (l, l+16), GP<M>::tail_set), so
-the tables are per m, not per padded size.  No GPU is needed to build a case."""
+the tables are per m, not per padded size.  The 'scale' family holds fits and means whose Cholesky
+pivots leave the range of the short sqrt / reciprocal sequences.  No GPU is needed to build a case."""
 import functools
 
 import numpy as np
@@ -344,6 +345,147 @@ def batch_rows():
     return rows + [(m, form) for m in LANE_MS for form in ('lanes4', 'lanes1')]
 
 
+# ---------------------------------------------------------------------- the 'scale' family
+# Fits and means whose Cholesky pivots leave the range of the short sqrt / reciprocal sequences
+# (csrc/nngp_math.h in_mid_range: 2^-500 <= x < 2^500 (1 + 2^-20), i.e. 3.05e-151 .. 3.27e150), so
+# nngp_gpeval.h's wave-wide ballot falls back to sqrt() and 1.0 / ljj and the lanes kernels'
+# sqrt_rcp_exact rescales by 4^+-300.  Three kinds of fit, interleaved so that adjacent fits always
+# differ in kind -- a wave of four fits then holds in-range and out-of-range pivots at once:
+#   'ord'   sy in -8 .. -1, jitter 1e-20 or 1e-12 (every pivot in range)
+#   'high'  sy in SCALE_HIGH_SY: psy = 10^sy > 2^500 (1 + 2^-20).  10^150.6 = 3.98e150 is so close
+#           above it that the pivots of later columns (a_jj minus the squares of the row) are back
+#           inside: such a matrix crosses the boundary in the middle of its factorisation
+#   'low'   sy in SCALE_LOW_SY with the 1e-170 jitter: psy + jitter < 2^-500
+# on the 'smooth' set (well-conditioned at sx = -3, -2, so every -LML is finite).
+SCALE_JITTERS = np.array([-170.0, -20.0, -12.0])
+SCALE_HIGH_SY = (150.6, 151.0, 160.0)
+SCALE_LOW_SY = (-151.0, -160.0)
+SCALE_SX = (-3.0, -2.0)
+SCALE_MS = (10, 15, 20, 33, 64)           # (33, 64: the nn_exp_nonpos_sep kernels; 10, 15: the lanes kernels)
+SCALE_NFITS = 19                          # five waves of four, the last partial; two workgroups up to M = 32
+SCALE_SETTINGS = tuple((0.1, k) for k in (3, 9, 11, 400))
+SCALE_KINDS = ('ord', 'high', 'low')
+MID_LO, MID_HI = float.fromhex('0x1p-500'), float.fromhex('0x1.00001p+500')
+
+
+def mid_accepts(x):
+    """csrc/nngp_math.h in_mid_range, restated."""
+    return MID_LO <= x < MID_HI
+
+
+def scale_thetas(n, seed):
+    """(kind [n], jitter_idx [n], theta [n][2]): fit i is of kind SCALE_KINDS[i % 3]."""
+    rng = np.random.default_rng(seed)
+    kind = [SCALE_KINDS[i % 3] for i in range(n)]
+    jidx = np.zeros(n, dtype=np.int32)
+    theta = np.zeros((n, 2))
+    for i, k in enumerate(kind):
+        theta[i, 0] = SCALE_SX[int(rng.integers(0, 2))]
+        if k == 'ord':
+            theta[i, 1], jidx[i] = float(rng.integers(-8, 0)), 1 + (i // 3) % 2
+        elif k == 'high':
+            theta[i, 1], jidx[i] = SCALE_HIGH_SY[(i // 3) % 3], (i // 3 + 1) % 3
+        else:
+            theta[i, 1], jidx[i] = SCALE_LOW_SY[(i // 3) % 2], 0
+    return kind, jidx, theta
+
+
+def scale_pivots(D2, theta, jitter_exp):
+    """The Cholesky pivots of K = psy exp(c D2) + jitter I by the oracle (orc_potf2 on the matrix
+    gp_factor builds): pivot 0 exactly, the later ones as L_jj^2; None where the factorisation fails."""
+    import ctypes
+    import oracle as O
+    L = O.lib()
+    m = D2.shape[0]
+    c = -0.5 * (1 / L.nn_pow10(float(theta[0])))
+    psy = L.nn_pow10(float(theta[1]))
+    K = np.array([[psy * L.nn_exp(c * D2[r, j]) for j in range(m)] for r in range(m)])
+    K[np.diag_indices(m)] += float(10.0 ** jitter_exp)
+    first = float(K[0, 0])
+    rinv = np.empty(m)
+    dp = ctypes.POINTER(ctypes.c_double)
+    if L.orc_potf2(m, K.ctypes.data_as(dp), rinv.ctypes.data_as(dp)):
+        return None
+    d = np.diag(K)
+    return np.concatenate([[first], d[1:] * d[1:]])
+
+
+def _check_scale_conditions(D2, kind, jidx, theta, need_crossing):
+    """Conditions on the recipe, from the oracle: every high or low matrix starts outside the set
+    in_mid_range accepts and, for the fit lists, some sy = 150.6 matrix comes back inside it at a
+    later column."""
+    crossing = 0
+    for k, a, th in zip(kind, jidx, theta):
+        piv = scale_pivots(D2, th, SCALE_JITTERS[a])
+        assert piv is not None, (k, th)
+        inside = [mid_accepts(p) for p in piv]
+        if k == 'ord':
+            assert all(inside), (k, th)
+            continue
+        assert not inside[0], (k, th, piv[0])
+        assert (piv[0] > MID_HI) == (k == 'high')
+        # (a margin of 1e-9 relative: L_jj^2 is the pivot up to two roundings)
+        if th[1] == 150.6 and any(mid_accepts(p * (1 - 1e-9)) and mid_accepts(p * (1 + 1e-9)) for p in piv[1:]):
+            crossing += 1
+    assert crossing >= 1 or not need_crossing
+
+
+@functools.lru_cache(maxsize=None)
+def scale_fit_case(m):
+    """(xm, ym, coord, jitter_idx, theta0, kind) of the SCALE_NFITS fits at m neighbours."""
+    import oracle as O
+    xm, ym, _ = fit_case(m, BATCH_D, 'smooth')
+    kind, jidx, theta0 = scale_thetas(SCALE_NFITS, 7000 + m)
+    coord = np.random.default_rng(7100 + m).integers(0, BATCH_D, SCALE_NFITS).astype(np.int32)
+    assert all(kind[i] != kind[i + 1] for i in range(SCALE_NFITS - 1))
+    D2 = O.d2_matrix(xm)
+    _check_scale_conditions(D2, kind, jidx, theta0, True)
+    for f in range(SCALE_NFITS):
+        assert np.isfinite(O.nlml(D2, ym[:, coord[f]], theta0[f], SCALE_JITTERS[jidx[f]])), (m, f)
+    for a in (xm, ym, coord, jidx, theta0):
+        a.setflags(write=False)
+    return xm, ym, coord, jidx, theta0, tuple(kind)
+
+
+@functools.lru_cache(maxsize=None)
+def scale_fit_oracle(m, fatol, maxfev):
+    """(theta [n][2], -LML [n], nfev [n]) of the oracle's Nelder-Mead on scale_fit_case(m): every
+    form shares this expectation.  Every fit ends at a finite -LML."""
+    import oracle as O
+    xm, ym, coord, jidx, theta0, _ = scale_fit_case(m)
+    D2 = O.d2_matrix(xm)
+    res = [O.nm_fit(D2, ym[:, coord[f]], theta0[f], SCALE_JITTERS[jidx[f]], fatol, fatol, maxfev)
+           for f in range(SCALE_NFITS)]
+    out = (np.array([r[0] for r in res]).reshape(-1, 2), np.array([r[1] for r in res]),
+           np.array([r[2] for r in res], dtype=np.int32))
+    assert np.isfinite(out[1]).all(), (m, maxfev)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def scale_rows():
+    """(m, form) of the 'scale' matrix: every form that exists for m."""
+    return [(m, form) for m in SCALE_MS for form in FORMS if form_accepts(form, m)]
+
+
+SCALE_MEAN_D = 13     # more than three waves of four coordinates, the last one partial
+
+
+@functools.lru_cache(maxsize=None)
+def scale_mean_case(m):
+    """(xm, ym, q, theta [d][2], jitter_idx [d], the oracle's means [d], kind) for nngp_gp_mean with
+    the same interleaved thetas; one case per padded size (m = the size itself)."""
+    import oracle as O
+    d = SCALE_MEAN_D
+    xm, ym, q = fit_case(m, d, 'smooth')
+    kind, jidx, theta = scale_thetas(d, 7200 + m)
+    _check_scale_conditions(O.d2_matrix(xm), kind, jidx, theta, False)
+    want = np.array([O.gp_mean(xm, ym[:, c], q, theta[c], SCALE_JITTERS[jidx[c]]) for c in range(d)])
+    assert np.isfinite(want).all(), m
+    return xm, ym, q, theta, jidx, want, tuple(kind)
+
+
 MEAN_D = (1, 3, 4, 5, 15, 16, 17, 33)
 # with the smallest jitter the coinciding pair of 'dup' fails the Cholesky at every m >= 3 under the
 # first; under the others it fails at most m and passes on rounding noise at the rest
@@ -362,6 +504,9 @@ def instantiations():
     for m, form in batch_rows():
         for n in BATCH_NFITS:
             seen.update(expected_form(m, BATCH_D, 9, 1, FORMS[form], api='fit_batch', n_fits=n)['kernels'])
+    for m, form in scale_rows():
+        seen.update(expected_form(m, BATCH_D, len(SCALE_JITTERS), 1, FORMS[form], api='fit_batch',
+                                  n_fits=SCALE_NFITS)['kernels'])
     for m in SWEEP_MS + (18,):   # (m = 18: the sweeps of tests/test_gpu_knn_matrix.py)
         for knobs in ({}, {'NNGP_HIT_MEAN': '0'}, {'NNGP_CHAIN': '1'}):
             seen.update(sweep_kernels(m, knobs))

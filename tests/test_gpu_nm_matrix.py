@@ -22,6 +22,11 @@ and the oracle against mpmath at the same neighbour counts); here
   of 4 fits per wave, 16 per workgroup and the work queue's threshold;
 * nngp_gp_mean at every m, on both sides of 4 and 16 coordinates per workgroup, with thetas whose
   Cholesky fails or passes on rounding noise alone;
+* the 'scale' family: nngp_nm_fit_batch on every form and nngp_gp_mean at every padded size with
+  signal variances 10^150.6 .. 10^160 and 10^-151 .. 10^-160 between ordinary ones, so that Cholesky
+  pivots leave the range of the short sqrt / reciprocal sequences (in_mid_range) in a wave that
+  also holds in-range fits -- the full-sequence branch of nngp_gpeval.h and the k = +-300 rescale of
+  sqrt_rcp_exact, which no other input reaches;
 * refused arguments, which launch nothing; and nngp_correction_sweep at every padded size (the
   packed batch of the guessed queries, gp_pre_kernel, chain_kernel).
 
@@ -217,6 +222,54 @@ def test_gp_mean_every_m_vs_oracle(gpu, m):
         assert np.array_equal(out.cpu().numpy(), want, equal_nan=True), d
         nans += int(np.isnan(want).sum())
     assert nans >= (1 if m >= 3 else 0)   # (m < 3: the first m rows do not hold the coinciding pair)
+
+
+# ------------------------------------------------------- d'. pivots outside the mid range
+def _scale_fit_batch(gpu, torch, m, fatol, maxfev):
+    xm, ym, coord, jidx, th0, _ = NC.scale_fit_case(m)
+    n = NC.SCALE_NFITS
+    theta = torch.full((n, 2), SENTINEL, dtype=torch.float64, device='cuda')
+    fval = torch.full((n,), SENTINEL, dtype=torch.float64, device='cuda')
+    nfev = torch.full((n,), -7, dtype=torch.int32, device='cuda')
+    jit, jp = gpu._lib.host_doubles(NC.SCALE_JITTERS)
+    xt, yt, tt = _t(torch, xm), _t(torch, ym), _t(torch, th0)
+    ct, jt = _t(torch, coord, torch.int32), _t(torch, jidx, torch.int32)
+    rc = gpu.lib().nngp_nm_fit_batch(m, NC.BATCH_D, xt.data_ptr(), yt.data_ptr(), n, ct.data_ptr(), jt.data_ptr(),
+                                     len(jit), jp, tt.data_ptr(), fatol, fatol, maxfev, theta.data_ptr(),
+                                     fval.data_ptr(), nfev.data_ptr(), None)
+    torch.cuda.synchronize()
+    return rc, theta.cpu().numpy(), fval.cpu().numpy(), nfev.cpu().numpy()
+
+
+@pytest.mark.parametrize('m,form', NC.scale_rows(), ids=lambda v: str(v))
+def test_fit_batch_scale_pivots_outside_the_mid_range_vs_oracle(gpu, m, form, monkeypatch):
+    """Fits whose pivots lie above 2^500 (1 + 2^-20) or below 2^-500, next to ordinary ones in the
+    same wave: nngp_gpeval.h's full sqrt / division branch, taken by the wave-wide ballot, and
+    the lanes kernels' 4^+-300 rescale; one matrix crosses the boundary while it is factorised.  The
+    caps 3, 9 and 11 end the fits while their simplices are still out of range."""
+    import torch
+    _set_form(monkeypatch, form)
+    for tol, maxfev in NC.SCALE_SETTINGS:
+        rc, theta, fval, nfev = _scale_fit_batch(gpu, torch, m, tol, maxfev)
+        gpu._lib.check(rc)
+        oth, ofv, one = NC.scale_fit_oracle(m, tol, maxfev)
+        assert np.array_equal(theta, oth) and np.array_equal(fval, ofv), maxfev
+        assert np.array_equal(nfev, one), maxfev
+
+
+@pytest.mark.parametrize('m', NC.MAXMS)
+def test_gp_mean_scale_thetas_vs_oracle(gpu, m):
+    """nngp_gp_mean with the same high and low thetas between ordinary ones, at every padded size."""
+    import torch
+    xm, ym, q, theta, jidx, want, _ = NC.scale_mean_case(m)
+    d = NC.SCALE_MEAN_D
+    jit, jp = gpu._lib.host_doubles(NC.SCALE_JITTERS)
+    out = torch.full((d,), SENTINEL, dtype=torch.float64, device='cuda')
+    xt, yt, qt, tt, jt = _t(torch, xm), _t(torch, ym), _t(torch, q), _t(torch, theta), _t(torch, jidx, torch.int32)
+    gpu._lib.check(gpu.lib().nngp_gp_mean(m, d, xt.data_ptr(), yt.data_ptr(), qt.data_ptr(), tt.data_ptr(),
+                                          jt.data_ptr(), len(jit), jp, out.data_ptr(), None))
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy(), want)
 
 
 # --------------------------------------------------------------------------- e. refusals

@@ -119,8 +119,9 @@ MP_THETAS = ((-3.0, -4.0), (-1.0, -6.0), (-5.0, -2.0))
 MP_JITTERS = (-12.0, -16.0)
 
 
-def _mp_case(mp, D2, kd2, y, theta, jit):
-    """(-LML, posterior mean) at 60 digits from the double inputs."""
+def _mp_case(mp, D2, kd2, y, theta, jit, tol=None):
+    """(-LML, posterior mean) at 60 digits from the double inputs.  tol: mpmath's absolute threshold
+    of positive-definiteness (its default, 1e-60, refuses a kernel matrix of entries ~1e-160)."""
     m = len(y)
     sx, sy = mp.mpf(10) ** mp.mpf(theta[0]), mp.mpf(10) ** mp.mpf(theta[1])
     k = lambda r2: sy * mp.exp(-mp.mpf(r2) / (2 * sx))
@@ -128,7 +129,7 @@ def _mp_case(mp, D2, kd2, y, theta, jit):
     for i in range(m):
         for j in range(i + 1):
             K[i, j] = K[j, i] = k(D2[i, j]) + (mp.mpf(jit) if i == j else 0)
-    L = mp.cholesky(K)
+    L = mp.cholesky(K, tol=tol)
     yv = [mp.mpf(v) for v in y]
     z = []
     for i in range(m):
@@ -191,6 +192,95 @@ def test_oracle_vs_mpmath_at_every_padded_edge(what, col):
           f'{min(conds):.3g} .. {max(conds):.3g}: oracle {e_or:.3g} (m={worst[0]} theta={worst[1]} '
           f'jitter=1e{worst[2]:.0f}), numpy/LAPACK {e_np:.3g}')
     assert min(conds) < 10 and max(conds) > 1e10   # the table spans well- and ill-conditioned K
+    assert e_or <= max(4.0, 2.0 * e_np)
+
+
+# ------------------------------------------------------------------------ the 'scale' family
+SCALE_MP_THETAS = (((-2.0, 150.6), -12.0), ((-3.0, 160.0), -20.0), ((-2.0, -151.0), -170.0), ((-3.0, -160.0), -170.0))
+
+
+def test_scale_rows_reach_the_dispatch_table():
+    """Every form at every scale m names kernels of the instantiation table, without the CU count:
+    both lanes kernels at 10 and 15, the packed, one-level, two-level and resume kernels at the
+    padded sizes 16 and 20, the packed and one-level ones at 48 and 64."""
+    rows = NC.scale_rows()
+    assert len(rows) == 11 + 11 + 9 + 5 + 5
+    reached = set()
+    for m, form in rows:
+        e = NC.expected_form(m, NC.BATCH_D, len(NC.SCALE_JITTERS), 1, NC.FORMS[form], api='fit_batch',
+                             n_fits=NC.SCALE_NFITS)
+        assert e['rc'] == NC.NNGP_OK and set(e['kernels']) <= set(EXPECTED_INSTANTIATIONS), (m, form)
+        reached.update(e['kernels'])
+    want = ([('nm_lane_kernel', m, 4) for m in (10, 15)] + [('nm_lane1_kernel', m) for m in (10, 15)] +
+            [('nm_fit_kernel', M, False) for M in (16, 20, 48, 64)] + [('nm_spec_kernel', M) for M in (16, 20, 48, 64)] +
+            [('nm_spec2_kernel', M, W) for M in (16, 20) for W in (0, 2, 4)])
+    assert sorted(reached, key=str) == sorted(want, key=str)
+    # the packed forms split the list over more than one workgroup, the last wave is partial
+    q = NC.expected_form(20, NC.BATCH_D, 3, 1, NC.FORMS['packed_static'], api='fit_batch', n_fits=NC.SCALE_NFITS)
+    assert q['mode'] == 'static' and q['nblocks'] == 2 and NC.SCALE_NFITS % 4 != 0
+
+
+def test_scale_case_conditions():
+    """The conditions the 'scale' GPU tests rely on, from the oracle: adjacent fits differ in kind,
+    every high or low matrix starts outside the set in_mid_range accepts (nm_cases checks that, and
+    the crossing matrix at sy = 150.6, while it builds a case), every start and every result has a
+    finite -LML, and the caps 3, 9, 11 end every fit there while 400 lets every fit converge."""
+    assert NC.mid_accepts(2.0 ** -500) and not NC.mid_accepts(np.nextafter(2.0 ** -500, 0))
+    assert NC.mid_accepts(np.nextafter(NC.MID_HI, 0)) and not NC.mid_accepts(NC.MID_HI) and NC.mid_accepts(2.0 ** 500)
+    for m in NC.SCALE_MS:
+        xm, ym, coord, jidx, th0, kind = NC.scale_fit_case(m)
+        assert all(kind[i] != kind[i + 1] for i in range(len(kind) - 1))
+        assert all({'ord', 'high', 'low'} == set(kind[w:w + 4]) for w in range(0, len(kind) - 3, 4))
+        high, low = [k == 'high' for k in kind], [k == 'low' for k in kind]
+        assert set(th0[high, 1]) == set(NC.SCALE_HIGH_SY) and set(th0[low, 1]) == set(NC.SCALE_LOW_SY)
+        assert set(th0[:, 0]) == set(NC.SCALE_SX) and np.all(NC.SCALE_JITTERS[jidx[low]] == -170.0)
+        for tol, maxfev in NC.SCALE_SETTINGS:
+            theta, fval, nfev = NC.scale_fit_oracle(m, tol, maxfev)
+            assert np.isfinite(fval).all() and np.isfinite(theta).all()
+            assert np.all(nfev == maxfev) if maxfev < 400 else np.all(nfev < 400)
+        # at the cap of 3 the high and low fits still sit at their out-of-range starts
+        theta3 = NC.scale_fit_oracle(m, 0.1, 3)[0]
+        assert np.all(theta3[high, 1] > 150.5) and np.all(theta3[low, 1] < -150.9)
+    for M in NC.MAXMS:
+        *_, want, kind = NC.scale_mean_case(M)
+        assert np.isfinite(want).all() and len(set(kind)) == 3
+
+
+@functools.lru_cache(maxsize=None)
+def _mp_scale_table():
+    mp = pytest.importorskip('mpmath').mp
+    mp.dps = 60
+    eps = np.finfo(float).eps
+    rows = []
+    for m in NC.SCALE_MS:
+        xm, ym, q = NC.fit_case(m, NC.BATCH_D, 'smooth')
+        y = np.ascontiguousarray(ym[:, 0])
+        D2 = O.d2_matrix(xm)
+        kd2 = O.d2_matrix(np.vstack([xm, q]))[-1, :-1].copy()
+        for theta, je in SCALE_MP_THETAS:
+            jit = float(10.0 ** je)
+            f_mp, mean_mp = _mp_case(mp, D2, kd2, y, theta, jit, tol=mp.mpf(0))
+            f_np, mean_np, cond = _np_case(D2, kd2, y, theta, jit)
+            f_or, mean_or = O.nlml(D2, y, theta, je), O.gp_mean(xm, y, q, theta, je)
+            assert np.isfinite([f_np, mean_np, f_or, mean_or]).all(), (m, theta, je)
+            sc_f = eps * cond * max(1.0, abs(float(f_mp)))
+            sc_m = eps * cond * max(1.0, abs(float(mean_mp)))
+            rows.append((m, theta, je, cond,
+                         float(abs(mp.mpf(f_or) - f_mp)) / sc_f, float(abs(mp.mpf(f_np) - f_mp)) / sc_f,
+                         float(abs(mp.mpf(mean_or) - mean_mp)) / sc_m, float(abs(mp.mpf(mean_np) - mean_mp)) / sc_m))
+    return rows
+
+
+@pytest.mark.parametrize('what,col', [('nlml', 4), ('gp_mean', 6)])
+def test_oracle_vs_mpmath_scale_rows(what, col):
+    """The oracle that judges the 'scale' rows, at their signal variances 10^150.6, 10^160, 10^-151
+    and 10^-160 (jitter 1e-170 under the low ones): the same yardstick and bound as above."""
+    rows = _mp_scale_table()
+    assert len(rows) == 20
+    e_or, e_np = max(r[col] for r in rows), max(r[col + 1] for r in rows)
+    worst = max(rows, key=lambda r: r[col])
+    print(f'{what}, scale rows: largest err / (eps * cond2(K) * max(1, |f|)) over {len(rows)} cases: oracle '
+          f'{e_or:.3g} (m={worst[0]} theta={worst[1]} jitter=1e{worst[2]:.0f}), numpy/LAPACK {e_np:.3g}')
     assert e_or <= max(4.0, 2.0 * e_np)
 
 
