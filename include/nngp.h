@@ -320,6 +320,21 @@ int nngp_gpfull_lml(const double *X, int64_t rows, int d, const double *Y, int n
                     const int32_t *coord, const double *jitter_exp, const double *theta,
                     double *fval_out, double *alpha_out, void *stream);
 
+/* nngp_gpfull_factor: a TEST AND DIAGNOSTIC entry with no reference call site (the reference never
+ * exposes its Cholesky factor).  nngp_gpfull_lml's arguments and results, computed by the same
+ * launches under the same knobs and slab chunking (no kernel and no arithmetic of its own), plus
+ * copies of what they leave behind, all DEVICE:
+ *   factor_out [n_pts][rows+1][rows+1]: per point the factored matrix [K; y^T].  ONLY the lower
+ *              triangle of rows 0..rows-1 (L, diagonal included) and columns 0..rows-1 of row
+ *              `rows` (z^T = (L^-1 y)^T) are defined; everything else, and every entry of a point
+ *              whose fail flag is set, is unspecified.
+ *   fail_out   [n_pts] int32: 1 where a pivot was not > 0 (fval_out is then +inf), else 0.
+ *   d2_out     [rows][rows] = cdist(X, X, 'sqeuclidean'), or NULL. */
+int nngp_gpfull_factor(const double *X, int64_t rows, int d, const double *Y, int n_pts,
+                       const int32_t *coord, const double *jitter_exp, const double *theta,
+                       double *fval_out, double *alpha_out, double *factor_out, int32_t *fail_out,
+                       double *d2_out, void *stream);
+
 /* nngp_gpfull_fit: n_fit Nelder-Mead fits (GPjax_p.opt_theta, models.py:329-335: scipy NM,
  * fatol/xatol, maxiter = maxfev) of -LML for (coord[f], jitter_exp[f]) from theta0[f], all fits
  * advancing together, one batched evaluation per round; replaces pool.map(_get_opt_par, ...)

@@ -26,7 +26,7 @@ EXPORTS = ['nngp_abi_version', 'nngp_last_error', 'nngp_device_count', 'nngp_rk_
            'nngp_rk_traj', 'nngp_rk_adaptive',
            'nngp_rhs_batch', 'nngp_parareal_update', 'nngp_knn', 'nngp_nm_fit_batch',
            'nngp_gp_mean', 'nngp_predict', 'nngp_correction_sweep', 'nngp_gpfull_lml', 'nngp_gpfull_fit',
-           'nngp_gpfull_mean', 'nngp_predict_range', 'nngp_chain_stats', 'nngp_sweep_late_reruns', 'nngp_shutdown',
+           'nngp_gpfull_mean', 'nngp_gpfull_factor', 'nngp_predict_range', 'nngp_chain_stats', 'nngp_sweep_late_reruns', 'nngp_shutdown',
            'nngp_comm_available', 'nngp_comm_unique_id', 'nngp_comm_init', 'nngp_comm_size', 'nngp_comm_destroy',
            'nngp_allgather_states', 'nngp_correction_sweep_sharded', 'nngp_correction_sweep_sharded_emulated',
            'nngp_elm_hidden', 'nngp_elm_predict', 'nngp_elm_sweep', 'nngp_poly_create', 'nngp_poly_destroy',
@@ -87,6 +87,7 @@ def lib():
                                         _vp, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), _vp]
     _ip = ctypes.POINTER(ctypes.c_int32)
     L.nngp_gpfull_lml.argtypes = [_vp, i64, i32, _vp, i32, _ip, _dp, _dp, _dp, _vp, _vp]
+    L.nngp_gpfull_factor.argtypes = [_vp, i64, i32, _vp, i32, _ip, _dp, _dp, _dp, _vp, _vp, _vp, _vp, _vp]
     L.nngp_gpfull_fit.argtypes = [_vp, i64, i32, _vp, i32, _ip, _dp, _dp, dbl, dbl, i32, _dp, _dp, _ip, _ip, _vp]
     L.nngp_gpfull_mean.argtypes = [_vp, i64, i32, _vp, _vp, _vp, _vp, _vp, _vp]
     L.nngp_chain_stats.argtypes = [ctypes.POINTER(i64)]

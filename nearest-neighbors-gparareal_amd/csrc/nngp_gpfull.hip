@@ -22,7 +22,8 @@
 // The trailing update runs on the FP64 MFMA (same peak rate as the VALU, but operands come from
 // registers: two LDS reads per 1 024 multiply-adds instead of one per FMA).  The arithmetic order
 // of LAPACK's blocked potrf is not reproduced (it is third-party and build-dependent); parity is
-// to tolerance (tests/test_gpu_gpfull.py).
+// to tolerance (tests/test_gpu_gpfull.py), and the factor itself (nngp_gpfull_factor)
+// is held elementwise to its backward-error bounds (tests/test_gpu_gpfull_factor.py).
 // The Nelder-Mead state machines (nngp_nm.h, scipy's semantics) run on the host, one per fit.
 #include <cmath>
 #include <vector>
@@ -974,9 +975,11 @@ static int gpf_batch_cap(int n, int n_fit) {
 
 using namespace nngp;
 
-extern "C" int nngp_gpfull_lml(const double *X, int64_t rows, int d, const double *Y, int n_pts,
-                               const int32_t *coord, const double *jitter_exp, const double *theta,
-                               double *fval_out, double *alpha_out, void *stream) {
+// nngp_gpfull_lml, and nngp_gpfull_factor's copies of what it leaves behind: factor_out / fail_out
+// (each chunk's A slab and fail flags) and d2_out (the hoisted D^2), all DEVICE, each may be null
+static int gpf_lml_run(const double *X, int64_t rows, int d, const double *Y, int n_pts, const int32_t *coord,
+                       const double *jitter_exp, const double *theta, double *fval_out, double *alpha_out,
+                       double *factor_out, int32_t *fail_out, double *d2_out, void *stream) {
     NNGP_REQUIRE(X && Y && coord && jitter_exp && theta && fval_out, "null argument");
     int rc = gpf_check(rows, d, n_pts);
     if (rc) return rc;
@@ -987,6 +990,8 @@ extern "C" int nngp_gpfull_lml(const double *X, int64_t rows, int d, const doubl
     if (rc) return rc;
     hipLaunchKernelGGL(gpf_d2_kernel, dim3((n + 15) / 16, (n + 15) / 16), dim3(16, 16), 0, st, X, n, d, w.D2);
     NNGP_LAUNCH_CHECK();
+    if (d2_out)
+        NNGP_HIP_CHECK(hipMemcpyAsync(d2_out, w.D2, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToDevice, st));
     std::vector<GPPoint> hp((size_t)n_pts);
     for (int i = 0; i < n_pts; i++) {
         NNGP_REQUIRE(coord[i] >= 0 && coord[i] < d, "coordinate %d out of range", coord[i]);
@@ -1000,10 +1005,34 @@ extern "C" int nngp_gpfull_lml(const double *X, int64_t rows, int d, const doubl
                       w.Lpan, st);
         if (rc) return rc;
         NNGP_HIP_CHECK(hipMemcpyAsync(hf.data() + s, w.fval, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+        const size_t mm = (size_t)(n + 1) * (n + 1);
+        if (factor_out)
+            NNGP_HIP_CHECK(hipMemcpyAsync(factor_out + (size_t)s * mm, w.A, sizeof(double) * nb * mm,
+                                          hipMemcpyDeviceToDevice, st));
+        if (fail_out)
+            NNGP_HIP_CHECK(hipMemcpyAsync(fail_out + s, w.fail, sizeof(int32_t) * nb, hipMemcpyDeviceToDevice, st));
     }
     NNGP_HIP_CHECK(hipStreamSynchronize(st));
     for (int i = 0; i < n_pts; i++) fval_out[i] = hf[i];
     return NNGP_OK;
+}
+
+extern "C" int nngp_gpfull_lml(const double *X, int64_t rows, int d, const double *Y, int n_pts,
+                               const int32_t *coord, const double *jitter_exp, const double *theta,
+                               double *fval_out, double *alpha_out, void *stream) {
+    return gpf_lml_run(X, rows, d, Y, n_pts, coord, jitter_exp, theta, fval_out, alpha_out, nullptr, nullptr, nullptr,
+                       stream);
+}
+
+// Test and diagnostic entry (include/nngp.h): nngp_gpfull_lml's own pipeline, with the factored
+// slabs, the fail flags and D^2 copied out -- no kernel and no arithmetic of its own.
+extern "C" int nngp_gpfull_factor(const double *X, int64_t rows, int d, const double *Y, int n_pts,
+                                  const int32_t *coord, const double *jitter_exp, const double *theta,
+                                  double *fval_out, double *alpha_out, double *factor_out, int32_t *fail_out,
+                                  double *d2_out, void *stream) {
+    NNGP_REQUIRE(factor_out && fail_out, "null argument");
+    return gpf_lml_run(X, rows, d, Y, n_pts, coord, jitter_exp, theta, fval_out, alpha_out, factor_out, fail_out,
+                       d2_out, stream);
 }
 
 extern "C" int nngp_gpfull_fit(const double *X, int64_t rows, int d, const double *Y, int n_fit,

@@ -11,6 +11,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import gpf_cases as GC
 import gpfull as GF
 from conftest import golden
 
@@ -36,6 +37,27 @@ def _lml(gpu, torch, x, y, coords, jitters, thetas, alpha=False):
         th.ctypes.data_as(dp), fv.ctypes.data_as(dp), al.data_ptr() if alpha else None, None))
     torch.cuda.synchronize()
     return fv, (al.cpu().numpy() if alpha else None)
+
+
+def _factors(gpu, torch, x, y, coords, jitters, thetas):
+    """The same batch through nngp_gpfull_factor: (fval, alpha, the (n+1) x n factors [L; z^T])."""
+    n_pts, n = len(coords), x.shape[0]
+    X, Y = _dev(torch, x), _dev(torch, y)
+    c = np.ascontiguousarray(coords, dtype=np.int32)
+    jx = np.ascontiguousarray(jitters, dtype=float)
+    th = np.ascontiguousarray(thetas, dtype=float).reshape(n_pts, 2)
+    fv = np.empty(n_pts)
+    al = torch.empty((n_pts, n), dtype=torch.float64, device='cuda')
+    A = torch.empty((n_pts, n + 1, n + 1), dtype=torch.float64, device='cuda')
+    fail = torch.empty((n_pts,), dtype=torch.int32, device='cuda')
+    ip = ctypes.POINTER(ctypes.c_int32)
+    dp = ctypes.POINTER(ctypes.c_double)
+    gpu._lib.check(gpu.lib().nngp_gpfull_factor(
+        X.data_ptr(), n, x.shape[1], Y.data_ptr(), n_pts, c.ctypes.data_as(ip), jx.ctypes.data_as(dp),
+        th.ctypes.data_as(dp), fv.ctypes.data_as(dp), al.data_ptr(), A.data_ptr(), fail.data_ptr(), None, None))
+    torch.cuda.synchronize()
+    A = A.cpu().numpy()
+    return fv, al.cpu().numpy(), [GC.trapezoid(A[b], n) for b in range(n_pts)]
 
 
 def _tol(x, theta, jit):
@@ -73,7 +95,9 @@ def test_gpfull_lml_and_weights_vs_oracle(gpu, n, order, monkeypatch):
     """Panel edges (31/32/33 and 63/64/65), several panels, and a 600-row set (the size GParareal
     reaches), in every factor order (NNGP_GPF_ORDER / NNGP_GPF_FMA; each against the oracle, as
     they round differently); a one-matrix slab (NNGP_GPF_SLAB_MB) and the unfused diagonal factor
-    (NNGP_GPF_FUSE=0) bitwise the defaults."""
+    (NNGP_GPF_FUSE=0) bitwise the defaults.  The weights are held to the norm-wise residual and,
+    against the GPU's own factor (nngp_gpfull_factor), to the elementwise bound of the back
+    substitution; the factor itself is the subject of tests/test_gpu_gpfull_factor.py."""
     import torch
     for k, v in ORDERS[order].items():
         monkeypatch.setenv(k, v)
@@ -94,6 +118,8 @@ def test_gpfull_lml_and_weights_vs_oracle(gpu, n, order, monkeypatch):
     # sigma_x = 0: NaN kernel -> failed Cholesky -> +inf (the reference would raise from
     # solve_triangular's finite check here, so there is no reference value to compare with)
     assert np.isinf(fv[3]) and fv[3] > 0
+    fvf, alf, Fs = _factors(gpu, torch, x, y, coords, jit, thetas)
+    assert np.array_equal(fvf, fv) and np.array_equal(np.nan_to_num(alf[:3]), np.nan_to_num(al[:3]))
     for i in range(3):
         ref = GF.gp_nlml(x, y[:, coords[i]], np.array(thetas[i]), jit[i])
         assert _close(fv[i], ref, _tol(x, np.array(thetas[i]), jit[i])), (n, i, fv[i], ref)
@@ -103,6 +129,9 @@ def test_gpfull_lml_and_weights_vs_oracle(gpu, n, order, monkeypatch):
             yy = y[:, coords[i]]
             res = np.abs(K @ al[i] - yy).max()
             assert res <= 1e-12 * (np.abs(K).sum(1).max() * np.abs(al[i]).max() + np.abs(yy).max()), (n, i, res)
+            # and elementwise against the GPU's own factor: |L^T alpha - z|_i <= gamma_n (|L^T||alpha|)_i
+            # (Higham Thm 8.5; tests/gpf_cases.py), which does not grow with |alpha| ~ 1e10 as the line above
+            assert GC.alpha_check(Fs[i], al[i]) <= 1.0, (n, i, GC.alpha_check(Fs[i], al[i]))
 
 
 def test_gpfull_weights_beyond_the_lds_vector(gpu):
