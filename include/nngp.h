@@ -57,9 +57,12 @@ enum nngp_system_kind {
     NNGP_SYS_FHN_PDE = 8,           /* systems.py:291-398, nx = d_x, d = 2*d_x*d_x         */
     NNGP_SYS_DIFFREACT = 9,         /* systems.py:463-577, nx = d_x (3..32), d = 2*nx*nx, state u | v,
                                        param[0..2] = Du, Dv, k; zero-flux walls             */
-    NNGP_SYS_POLY = 10              /* a caller-defined polynomial field (the reference's extension point,
+    NNGP_SYS_POLY = 10,             /* a caller-defined polynomial field (the reference's extension point,
                                        a subclass of ODE: systems.py:23-61), nx = the table's handle
                                        from nngp_poly_create, 1 <= d <= 2048                  */
+    NNGP_SYS_FUNC = 11              /* a caller-defined field of monomials over the state and over
+                                       elementary-function atoms of it (sin, cos, exp, log, 1/x, sqrt),
+                                       nx = the table's handle from nngp_func_create, 1 <= d <= 2048 */
 };
 
 /* Explicit Runge-Kutta tableaux, RK.py:30-48 (value = order). */
@@ -83,8 +86,8 @@ enum nngp_step_mode { NNGP_STEP_FIXED = 0, NNGP_STEP_LINSPACE = 1, NNGP_STEP_CON
 typedef struct nngp_system {
     int32_t kind;        /* enum nngp_system_kind                                         */
     int32_t d;           /* state dimension                                               */
-    int32_t nx;          /* grid points per axis (Burgers: d; FHN_PDE, DIFFREACT: d_x); POLY: the
-                            table's handle; else 0                                        */
+    int32_t nx;          /* grid points per axis (Burgers: d; FHN_PDE, DIFFREACT: d_x); POLY, FUNC:
+                            the table's handle; else 0                                    */
     int32_t normalized;  /* 0: identity, 1: '-11' wrapper                                 */
     double param[4];     /* HOPF: [0]=maxtime (tspan[1]); BURGERS: [0]=nu; DIFFREACT: [0..2]=Du, Dv, k;
                             else unused                                                   */
@@ -150,7 +153,8 @@ int nngp_rk_traj(const nngp_system *sys, int tableau, int step_mode, int n_slice
  * Stream-ordered, no host synchronisation; uF may alias u0; n_slices = 0 is a no-op.  Exact build
  * only: there is no NNGP_STEP_CONTRACT form.  Field systems take d <= 2048.
  * NNGP_E_ARG before any HIP call: unknown method; nf < 1; rtol <= 0, atol < 0 or a non-finite
- * tolerance; first_step < 0; max_attempts < 1; an unknown or destroyed NNGP_SYS_POLY handle.
+ * tolerance; first_step < 0; max_attempts < 1; an unknown or destroyed NNGP_SYS_POLY or
+ * NNGP_SYS_FUNC handle.
  * t0, t1: DEVICE [n_slices]; u0, uF: DEVICE [n_slices][sys->d].                              */
 enum nngp_adaptive_method { NNGP_RK23 = 23, NNGP_RK45 = 45 };
 int nngp_rk_adaptive(const nngp_system *sys, int method, int n_slices,
@@ -183,6 +187,38 @@ int nngp_rhs_batch(const nngp_system *sys, int n, const double *u, double *out, 
 int nngp_poly_create(int d, int n_terms, const int32_t *row_ptr_host, const double *coef_host,
                      const int16_t *idx_host, int32_t *handle_out);
 int nngp_poly_destroy(int32_t handle);
+
+/* Fields with elementary-function atoms (NNGP_SYS_FUNC): a polynomial table whose monomials range
+ * over the extended vector w = [u_0 .. u_{d-1}, atom_0 .. atom_{n_atoms-1}].  Atom q is fn(x) of
+ *     x = a*u[i];   if j >= 0: x = x + c*u[j];   if has_b: x = x + b
+ * one rounding per operation in that order (an absent part is not an added 0.0), with fn one of
+ * enum nngp_func_fn: the library's own sine (the one NNGP_SYS_THOMAS_LABYRINTH uses), cosine, exp
+ * and log -- fully specified routines, the same bits on every device -- and the IEEE 1.0/x and
+ * sqrt(x).  Atoms read the state only.  A domain error gives what the routine gives (NaN, inf).
+ * Terms, rows and their arithmetic are nngp_poly_create's, the term indices in [0, d + n_atoms);
+ * with n_atoms = 0 the kind is NNGP_SYS_POLY bit for bit.  The contracted build
+ * (NNGP_STEP_CONTRACT) may fuse the atom's argument and the row sum.  Restated in
+ * tests/func_ref.py.  All arguments are HOST arrays, copied; nothing is launched.
+ *   Checked here, before any HIP call (the kernels trust a registered table): 1 <= d <= 2048,
+ *   0 <= n_atoms <= 2048, 0 <= n_terms <= 1048576; per atom fn in 1..6, i in [0, d), j = -1 or in
+ *   [0, d), has_b 0 or 1, a, c and b finite; row_ptr as for nngp_poly_create; every term index -1
+ *   or in [0, d + n_atoms) with no -1 before a real index; every coefficient finite.
+ * *handle_out >= 1 goes into nngp_system.nx of a system of kind NNGP_SYS_FUNC with the same d.
+ * Every propagator entry point and nngp_rhs_batch refuses an unknown or destroyed handle and
+ * another d with NNGP_E_ARG.  The device copy is uploaded per device on first use and kept.
+ * nngp_func_destroy frees a table (its slot may be handed out again); nngp_shutdown frees all. */
+enum nngp_func_fn { NNGP_FN_SIN = 1, NNGP_FN_COS = 2, NNGP_FN_EXP = 3, NNGP_FN_LOG = 4, NNGP_FN_RECIP = 5,
+                    NNGP_FN_SQRT = 6 };
+typedef struct nngp_func_atom {
+    int32_t fn;          /* enum nngp_func_fn                                             */
+    int32_t i, j;        /* state indices; j = -1: no second component                    */
+    int32_t has_b;       /* 1: the offset b is added, 0: it is absent                     */
+    double a, c, b;      /* c is unused when j = -1, b when has_b = 0 (both still finite) */
+} nngp_func_atom;
+int nngp_func_create(int d, int n_atoms, const nngp_func_atom *atoms_host, int n_terms,
+                     const int32_t *row_ptr_host, const double *coef_host, const int16_t *idx_host,
+                     int32_t *handle_out);
+int nngp_func_destroy(int32_t handle);
 
 /* Elementwise  out = (a - b) + c   (c may be NULL: out = a - b), n doubles, DEVICE.
  *   Parareal update with the classic model: u = (uF_prev - uG_prev) + uG_new

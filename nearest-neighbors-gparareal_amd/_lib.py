@@ -18,6 +18,8 @@ CSRC = os.path.join(HERE, 'csrc')
 SYS_LORENZ, SYS_HOPF, SYS_THOMAS_LABYRINTH, SYS_FHN_ODE, SYS_ROSSLER = 0, 1, 2, 3, 4
 SYS_BRUSSELATOR, SYS_DBL_PEND, SYS_BURGERS, SYS_FHN_PDE, SYS_DIFFREACT = 5, 6, 7, 8, 9
 SYS_POLY = 10
+SYS_FUNC = 11
+FUNC_FN = {'sin': 1, 'cos': 2, 'exp': 3, 'log': 4, 'recip': 5, 'sqrt': 6}   # enum nngp_func_fn
 TABLEAU = {'RK1': 1, 'RK2': 2, 'RK4': 4, 'RK8': 8}
 ADAPTIVE = {'RK23': 23, 'RK45': 45}   # enum nngp_adaptive_method
 STEP_FIXED, STEP_LINSPACE, STEP_CONTRACT = 0, 1, 16
@@ -30,8 +32,15 @@ EXPORTS = ['nngp_abi_version', 'nngp_last_error', 'nngp_device_count', 'nngp_rk_
            'nngp_comm_available', 'nngp_comm_unique_id', 'nngp_comm_init', 'nngp_comm_size', 'nngp_comm_destroy',
            'nngp_allgather_states', 'nngp_correction_sweep_sharded', 'nngp_correction_sweep_sharded_emulated',
            'nngp_elm_hidden', 'nngp_elm_predict', 'nngp_elm_sweep', 'nngp_poly_create', 'nngp_poly_destroy',
+           'nngp_func_create', 'nngp_func_destroy',
            'nngp_knn_mean', 'nngp_knn_mean_sweep']
 MODEL_PARAREAL, MODEL_NNGP, MODEL_GPFULL = 0, 1, 2
+
+
+class CFuncAtom(ctypes.Structure):
+    """struct nngp_func_atom"""
+    _fields_ = [('fn', ctypes.c_int32), ('i', ctypes.c_int32), ('j', ctypes.c_int32), ('has_b', ctypes.c_int32),
+                ('a', ctypes.c_double), ('c', ctypes.c_double), ('b', ctypes.c_double)]
 
 
 class NNGPError(RuntimeError):
@@ -113,6 +122,9 @@ def lib():
                                  i32, i32, i32, _vp, _vp, ctypes.POINTER(ctypes.c_float), _vp]
     L.nngp_poly_create.argtypes = [i32, i32, _ip, _dp, ctypes.POINTER(ctypes.c_int16), _ip]
     L.nngp_poly_destroy.argtypes = [ctypes.c_int32]
+    L.nngp_func_create.argtypes = [i32, i32, ctypes.POINTER(CFuncAtom), i32, _ip, _dp, ctypes.POINTER(ctypes.c_int16),
+                                   _ip]
+    L.nngp_func_destroy.argtypes = [ctypes.c_int32]
     L.nngp_knn_mean.argtypes = [_vp, _vp, i64, i32, _vp, i32, _ip, i32, _vp, _vp, _vp, _vp, _vp]
     L.nngp_knn_mean_sweep.argtypes = [ctypes.POINTER(CSystem), i32, i32, i64, _vp, i32, i32, _vp, _vp, _vp, _vp, i64,
                                       i32, _vp, ctypes.POINTER(ctypes.c_float), _vp]

@@ -91,6 +91,24 @@ int poly_table(const nngp_system *sys, PolyTable *out);
 int poly_device(const nngp_system *sys, const int32_t **row_ptr, const PolyTerm **terms);
 void poly_release();   // nngp_shutdown's part: every table, host and device
 
+// Fields with elementary-function atoms (NNGP_SYS_FUNC): the registry of
+// nngp_func.hip.  A table is the polynomial field's -- the same 16-byte term records, their indices
+// over the extended vector [u_0 .. u_{d-1}, atom_0 .. atom_{n_atoms-1}] -- and n_atoms records of
+// nngp_func_atom (include/nngp.h), which the kernels read as they were registered.
+constexpr int FUNC_MAX_ATOMS = 2048;         // with d <= 2048: a stage image [2][d + n_atoms] of 64 KB
+constexpr int FUNC_LANE_ATOMS = 4;           // lane form: d <= 4, at most 4 atoms and 16 terms
+struct FuncTable {             // a registered table as the host holds it
+    int d, n_atoms, n_terms;
+    const int32_t *row_ptr;         // HOST [d+1]
+    const PolyTerm *terms;          // HOST [n_terms]
+    const nngp_func_atom *atoms;    // HOST [n_atoms]
+};
+// as poly_table / poly_device / poly_release, for the handle of nngp_func_create in sys->nx
+int func_table(const nngp_system *sys, FuncTable *out);
+int func_device(const nngp_system *sys, const int32_t **row_ptr, const PolyTerm **terms,
+                const nngp_func_atom **atoms);
+void func_release();
+
 // A prepared coordinate of gp_pre_kernel: alpha rows 0..maxm-1 | c | psy | ok
 __host__ __device__ constexpr int HM_STRIDE(int maxm) { return maxm + 3; }
 

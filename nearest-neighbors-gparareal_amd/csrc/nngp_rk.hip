@@ -83,13 +83,14 @@ __global__ void __launch_bounds__(256) rhs_field_kernel(FieldArgs fa, const doub
         V[e] = fa.normalized ? ((x + 1) / 2) * fa.norm[d + e] + fa.norm[e] : x;
     }
     __syncthreads();
+    if constexpr (SYS == NNGP_SYS_FUNC) func_atoms_stage(V, fa, func_atoms_of(fa), threadIdx.x, blockDim.x);
     for (int e = threadIdx.x; e < d; e += blockDim.x) {
         double f;
         if constexpr (SYS == NNGP_SYS_BURGERS) {
             f = burgers_elem(V, e, d, fa);
         } else if constexpr (SYS == NNGP_SYS_DIFFREACT) {
             f = dr_elem(V, e, half, dr_neighbours(fa, e < half ? e : e - half, true), fa);
-        } else if constexpr (SYS == NNGP_SYS_POLY) {
+        } else if constexpr (table_sys(SYS)) {
             f = poly_elem(V, fa.p_row[e], fa.p_row[e + 1], fa.p_terms);
         } else if (e < half) {
             const Nbr5 nb = fhn_neighbours(fa.nx, e);
@@ -134,7 +135,8 @@ static int launch_rhs_field(const nngp_system *sys, int n, const double *u, doub
     FieldArgs fa;
     int rc = field_args(sys, fa);
     if (rc) return rc;
-    hipLaunchKernelGGL(rhs_field_kernel<SYS>, dim3(n), dim3(256), sizeof(double) * sys->d, st, fa, u, out);
+    hipLaunchKernelGGL(rhs_field_kernel<SYS>, dim3(n), dim3(256), sizeof(double) * image_doubles<SYS>(fa), st, fa, u,
+                       out);
     NNGP_LAUNCH_CHECK();
     return NNGP_OK;
 }
@@ -177,6 +179,7 @@ extern "C" int nngp_rhs_batch(const nngp_system *sys, int n, const double *u, do
     case NNGP_SYS_DIFFREACT: return launch_rhs_field<NNGP_SYS_DIFFREACT>(sys, n, u, out, st);
     // one evaluation has no step loop to keep the table in registers for: the field form at every d
     case NNGP_SYS_POLY: return launch_rhs_field<NNGP_SYS_POLY>(sys, n, u, out, st);
+    case NNGP_SYS_FUNC: return launch_rhs_field<NNGP_SYS_FUNC>(sys, n, u, out, st);
     default: set_error("unknown system kind %d", sys->kind); return NNGP_E_ARG;
     }
 }

@@ -13,11 +13,11 @@
 //
 // Two kernel shapes, chosen as nngp_rk_batch chooses (nngp_rk_kernels.h), on the same right-hand
 // sides:
-//   * lane kernel  (the seven ODEs; PolyODE with d <= 4 and at most 16 terms): one lane = one
+//   * lane kernel  (the seven ODEs; PolyODE with d <= 4 and at most 16 terms; FuncODE with at most 4 atoms besides): one lane = one
 //     slice, y, y_new and the S + 1 stage derivatives in VGPRs, no LDS, no barriers.  The lanes
 //     of a wave take different numbers of steps and reject independently (divergent control flow
 //     under the exec mask); a finished lane idles until its wave's last lane ends.
-//   * field kernel (Burgers, FHN-PDE, DiffReact, PolyODE up to d = 2048): one workgroup = one
+//   * field kernel (Burgers, FHN-PDE, DiffReact, PolyODE and FuncODE up to d = 2048): one workgroup = one
 //     slice, thread t owns elements t, t + BT, ... (at most 4 per thread), stage images in a
 //     double-buffered LDS array exactly as rk_field_kernel.  The error norm is reduced by wave 0
 //     from an LDS array of squares; thread 0 alone runs the controller and publishes the next
@@ -345,10 +345,18 @@ __global__ void __launch_bounds__(64) rk_adapt_poly_lane_kernel(PolyLaneArgs arg
     ad_lane_slice<NNGP_SYS_POLY_LANE + D, METHOD, NORM>(args, a, i);
 }
 
+template <int D, int METHOD, bool NORM>
+__global__ void __launch_bounds__(64) rk_adapt_func_lane_kernel(FuncLaneArgs args, AdArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_slices) return;
+    ad_lane_slice<NNGP_SYS_FUNC_LANE + D, METHOD, NORM>(args, a, i);
+}
+
 // ---------------------------------------------------------------------------------------------
 // field form
 //
-// LDS: [2][d] stage images | sq[EPT * BT] squares | ctl[2] = the next attempt's h, 8 * accept +
+// LDS: [2][d] stage images (NNGP_SYS_FUNC: [2][d + n_atoms], and a second barrier per evaluation of
+// f, behind the atoms: func_atoms_stage) | sq[EPT * BT] squares | ctl[2] = the next attempt's h, 8 * accept +
 // exit code.  Barriers per attempted step: one per evaluation of f (S of them) and the two of the
 // norm -- after the squares are written, and after thread 0 has published ctl.
 //
@@ -361,22 +369,25 @@ __global__ void __launch_bounds__(64) rk_adapt_poly_lane_kernel(PolyLaneArgs arg
 // ---------------------------------------------------------------------------------------------
 template <int SYS, int EPT, bool NORM> struct AdField {
     const FieldArgs &fa;
-    int d, half, buf;
+    int d, half, buf, W;   // W: doubles per image
     double *img;
     int e_[EPT];
     double mn[EPT], w[EPT], sc[EPT];
     Nbr5 nb[(SYS == NNGP_SYS_FHN_PDE) ? EPT : 1];
     DrNbr rnb[(SYS == NNGP_SYS_DIFFREACT) ? EPT : 1];
-    int pb[(SYS == NNGP_SYS_POLY) ? EPT : 1], pe[(SYS == NNGP_SYS_POLY) ? EPT : 1];
+    int pb[table_sys(SYS) ? EPT : 1], pe[table_sys(SYS) ? EPT : 1];
+    int tid_, BT_;
+    const nngp_func_atom *fatoms;
 
     __device__ __forceinline__ AdField(const FieldArgs &fa_, double *img_, int tid, int BT)
-        : fa(fa_), d(fa_.d), half(fa_.d / 2), buf(0), img(img_) {
+        : fa(fa_), d(fa_.d), half(fa_.d / 2), buf(0), W(image_doubles<SYS>(fa_)), img(img_), tid_(tid), BT_(BT), fatoms(nullptr) {
+        if constexpr (SYS == NNGP_SYS_FUNC) fatoms = func_atoms_of(fa_);
 #pragma unroll
         for (int r = 0; r < EPT; r++) {
             const int e = tid + r * BT;
             e_[r] = e;
             const bool ok = e < d;
-            if constexpr (SYS == NNGP_SYS_POLY) {
+            if constexpr (table_sys(SYS)) {
                 pb[r] = ok ? fa.p_row[e] : 0;
                 pe[r] = ok ? fa.p_row[e + 1] : 0;
             }
@@ -393,11 +404,12 @@ template <int SYS, int EPT, bool NORM> struct AdField {
     }
     // f_n(x) of the thread's elements: one stage of rk_field_kernel without the h (one barrier)
     __device__ __forceinline__ void rhs(const double *x, double *out) {
-        double *V = img + buf * d;
+        double *V = img + buf * W;
 #pragma unroll
         for (int r = 0; r < EPT; r++)
             if (e_[r] < d) V[e_[r]] = NORM ? (x[r] + 1) * w[r] + mn[r] : x[r];
         __syncthreads();
+        if constexpr (SYS == NNGP_SYS_FUNC) func_atoms_stage(V, fa, fatoms, tid_, BT_);
 #pragma unroll
         for (int r = 0; r < EPT; r++) {
             const int e = e_[r];
@@ -407,7 +419,7 @@ template <int SYS, int EPT, bool NORM> struct AdField {
                     f = burgers_elem(V, e, d, fa);
                 } else if constexpr (SYS == NNGP_SYS_DIFFREACT) {
                     f = dr_elem(V, e, half, rnb[r], fa);
-                } else if constexpr (SYS == NNGP_SYS_POLY) {
+                } else if constexpr (table_sys(SYS)) {
                     f = poly_elem(V, pb[r], pe[r], fa.p_terms);
                 } else {   // FHN_PDE, systems.py:365-366
                     if (e < half) {
@@ -454,7 +466,7 @@ __global__ void __launch_bounds__(EPT == 1 ? 256 : 512) rk_adapt_field_kernel(Fi
     const int slice = blockIdx.x;
     const int tid = threadIdx.x, BT = blockDim.x;
     const int d = fa.d, npad = EPT * BT;
-    double *sq = smem + 2 * d;
+    double *sq = smem + 2 * image_doubles<SYS>(fa);
     double *pub = sq + npad;   // ctl[2]
     AdField<SYS, EPT, NORM> F(fa, smem, tid, BT);
 
@@ -580,7 +592,7 @@ static void adapt_threads(int d, int &bt, int &ept) {
 
 template <int SYS, int METHOD, int EPT>
 static int adapt_field_ept(const FieldArgs &fa, int bt, const AdArgs &a, hipStream_t st) {
-    const size_t lds = sizeof(double) * (2 * (size_t)fa.d + (size_t)EPT * bt + 2);
+    const size_t lds = sizeof(double) * (2 * (size_t)image_doubles<SYS>(fa) + (size_t)EPT * bt + 2);
     if (fa.normalized)
         hipLaunchKernelGGL((rk_adapt_field_kernel<SYS, METHOD, EPT, true>), dim3(a.n_slices), dim3(bt), lds, st, fa, a);
     else
@@ -632,6 +644,38 @@ static int adapt_poly(const nngp_system *sys, const PolyTable &pt, const AdArgs 
     }
 }
 
+template <int D, int METHOD>
+static int adapt_func_lane(const nngp_system *sys, const FuncTable &ft, const AdArgs &a, hipStream_t st) {
+    FuncLaneArgs la{};
+    la.normalized = sys->normalized;
+    la.norm = sys->norm;
+    func_lane_tab(ft, la.tab);
+    const dim3 grid((a.n_slices + 63) / 64);
+    if (sys->normalized)
+        hipLaunchKernelGGL((rk_adapt_func_lane_kernel<D, METHOD, true>), grid, dim3(64), 0, st, la, a);
+    else
+        hipLaunchKernelGGL((rk_adapt_func_lane_kernel<D, METHOD, false>), grid, dim3(64), 0, st, la, a);
+    NNGP_LAUNCH_CHECK();
+    return NNGP_OK;
+}
+
+// NNGP_SYS_FUNC: the lane form while the table fits the kernel arguments, else the field form
+// (launch_func); the handle and d were checked by nngp_rk_adaptive
+template <int METHOD>
+static int adapt_func(const nngp_system *sys, const AdArgs &a, hipStream_t st) {
+    FuncTable ft;
+    int rc = func_table(sys, &ft);
+    if (rc) return rc;
+    NNGP_REQUIRE(!sys->normalized || sys->norm != nullptr, "normalized system needs norm[3d]");
+    if (!func_lane_fits(ft)) return adapt_field<NNGP_SYS_FUNC, METHOD>(sys, a, st);
+    switch (ft.d) {
+    case 1: return adapt_func_lane<1, METHOD>(sys, ft, a, st);
+    case 2: return adapt_func_lane<2, METHOD>(sys, ft, a, st);
+    case 3: return adapt_func_lane<3, METHOD>(sys, ft, a, st);
+    default: return adapt_func_lane<4, METHOD>(sys, ft, a, st);
+    }
+}
+
 template <int METHOD>
 static int adapt_sys(const nngp_system *s, const PolyTable &pt, const AdArgs &a, hipStream_t st) {
     switch (s->kind) {
@@ -646,6 +690,7 @@ static int adapt_sys(const nngp_system *s, const PolyTable &pt, const AdArgs &a,
     case NNGP_SYS_FHN_PDE: return adapt_field<NNGP_SYS_FHN_PDE, METHOD>(s, a, st);
     case NNGP_SYS_DIFFREACT: return adapt_field<NNGP_SYS_DIFFREACT, METHOD>(s, a, st);
     case NNGP_SYS_POLY: return adapt_poly<METHOD>(s, pt, a, st);
+    case NNGP_SYS_FUNC: return adapt_func<METHOD>(s, a, st);
     default: set_error("unknown system kind %d", s->kind); return NNGP_E_ARG;
     }
 }
@@ -672,6 +717,11 @@ extern "C" int nngp_rk_adaptive(const nngp_system *sys, int method, int n_slices
     PolyTable pt{};
     if (sys->kind == NNGP_SYS_POLY) {
         int rc = poly_table(sys, &pt);   // an unknown or destroyed handle, or another d
+        if (rc) return rc;
+    }
+    if (sys->kind == NNGP_SYS_FUNC) {
+        FuncTable ft{};
+        int rc = func_table(sys, &ft);
         if (rc) return rc;
     }
     if (n_slices == 0) return NNGP_OK;

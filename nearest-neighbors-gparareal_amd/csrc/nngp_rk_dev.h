@@ -186,6 +186,159 @@ template <> struct LaneSys<NNGP_SYS_POLY_LANE + 2> : PolyLane<2> {};
 template <> struct LaneSys<NNGP_SYS_POLY_LANE + 3> : PolyLane<3> {};
 template <> struct LaneSys<NNGP_SYS_POLY_LANE + 4> : PolyLane<4> {};
 
+// ---------------------------------------------------------------------------------------------
+// Fields with elementary-function atoms (NNGP_SYS_FUNC): monomials over the
+// extended vector [u_0 .. u_{d-1}, atom_0 .. atom_{n_atoms-1}], atom q = fn(a u[i] (+ c u[j]) (+ b)).
+// The six functions are the project's own routines (nngp_math.h, pinned to the oracle bit for bit)
+// and the IEEE 1.0/x and sqrt.
+// ---------------------------------------------------------------------------------------------
+// keeps a uniform `if` a scalar branch (see NNGP_POLY_KEEP_BRANCH above)
+#define NNGP_FUNC_KEEP_BRANCH() asm volatile("")
+
+// fn(x), fn in 1..6 (checked when the table was registered).  UNIFORM: fn is the same in every lane
+// (the lane form, the table in the kernel arguments), and each function stands behind a scalar
+// branch of its own, so a step pays for the functions its table names and for no other; a per-lane
+// select over six results would run all six.  The field form's threads hold different atoms and
+// diverge here by exec mask.
+template <bool UNIFORM>
+__device__ __forceinline__ double func_apply(unsigned fn, double x) {
+    double r;
+    if (fn == NNGP_FN_SIN) {
+        if constexpr (UNIFORM) NNGP_FUNC_KEEP_BRANCH();
+        r = nn_sin_pi(x);
+    } else if (fn == NNGP_FN_COS) {
+        if constexpr (UNIFORM) NNGP_FUNC_KEEP_BRANCH();
+        r = nn_cos(x);
+    } else if (fn == NNGP_FN_EXP) {
+        if constexpr (UNIFORM) NNGP_FUNC_KEEP_BRANCH();
+        r = nn_exp(x);
+    } else if (fn == NNGP_FN_LOG) {
+        if constexpr (UNIFORM) NNGP_FUNC_KEEP_BRANCH();
+        r = nn_log(x);
+    } else if (fn == NNGP_FN_RECIP) {
+        if constexpr (UNIFORM) NNGP_FUNC_KEEP_BRANCH();
+        r = 1.0 / x;
+    } else {
+        if constexpr (UNIFORM) NNGP_FUNC_KEEP_BRANCH();
+        r = sqrt(x);
+    }
+    return r;
+}
+
+// field form: atom A from the state part of the stage image V (the de-normalised state); the
+// argument in the contract's order, an absent part not replaced by + 0.0
+__device__ __forceinline__ double func_atom_value(const nngp_func_atom &A, const double *__restrict__ V) {
+    double x = A.a * V[A.i];
+    if (A.j >= 0) x = x + A.c * V[A.j];
+    if (A.has_b) x = x + A.b;
+    return func_apply<false>((unsigned)A.fn, x);
+}
+
+// Lane form (d <= 4, at most 4 atoms and 16 terms): the polynomial lane form's scheme -- the table
+// wave-uniform, by value in the kernel arguments, the 16 terms and the 4 atoms unrolled and nested so
+// that the first one past the table's count leaves by one taken branch -- with the atoms in slots
+// D .. D + n_atoms - 1 of the same 8-slot register array, hence 3-bit indices in the term
+// descriptors and a table type of its own (PolyLaneTab is what it was).
+struct FuncLaneTab {
+    double coef[POLY_LANE_TERMS];
+    // per term: bits 0-1 the number of factors, 2-4 / 5-7 / 8-10 their indices, 11-12 the row,
+    // 13 first term of its row, 14 last term of its row
+    uint16_t desc[POLY_LANE_TERMS];
+    int n;
+    double a[FUNC_LANE_ATOMS], c[FUNC_LANE_ATOMS], b[FUNC_LANE_ATOMS];
+    // per atom: bits 0-2 the function, 3-4 i, 5-6 j, 7 a second component is present, 8 b is present
+    uint16_t adesc[FUNC_LANE_ATOMS];
+    int n_atoms;
+};
+struct FuncLaneArgs : LaneArgs {
+    FuncLaneTab tab;
+};
+constexpr int NNGP_SYS_FUNC_LANE = 80;   // + D: not a value of enum nngp_system_kind
+
+// the atoms, into slots D .. D + n_atoms - 1: unrolled and nested like the terms, so the table stays
+// in scalar registers and an atom past the table's count leaves by one taken branch.  (A rolled loop
+// over the atoms was tried for its smaller code: a uniform index into the table moves the whole
+// argument struct to private memory, and with scalar selects instead the loop inside the stage loop
+// keeps the compiler from unrolling the stages at all from D = 2 on -- DESIGN.md 3.2e.)
+template <int D, int Q>
+__device__ __forceinline__ void func_lane_atoms(const FuncLaneTab &tab, int na, double (&x)[POLY_LANE_SLOTS]) {
+    if constexpr (Q < FUNC_LANE_ATOMS) {
+        if (Q < na) {
+            unsigned ds = tab.adesc[Q];
+            asm volatile("" : "+s"(ds));   // as the term descriptors: decoded inside the step
+            double v = tab.a[Q] * x[(ds >> 3) & 3u];
+            if (ds & (1u << 7)) {
+                NNGP_FUNC_KEEP_BRANCH();
+                v = v + tab.c[Q] * x[(ds >> 5) & 3u];
+            }
+            if (ds & (1u << 8)) {
+                NNGP_FUNC_KEEP_BRANCH();
+                v = v + tab.b[Q];
+            }
+            x[D + Q] = func_apply<true>(ds & 7u, v);
+            func_lane_atoms<D, Q + 1>(tab, na, x);
+        }
+    }
+}
+
+// poly_lane_terms with 3-bit factor indices
+template <int D, int T>
+__device__ __forceinline__ void func_lane_terms(const FuncLaneTab &tab, int n, const double (&x)[POLY_LANE_SLOTS],
+                                                double (&r)[POLY_LANE_D], double acc) {
+    if constexpr (T < POLY_LANE_TERMS) {
+        if (T < n) {
+            unsigned ds = tab.desc[T];
+            asm volatile("" : "+s"(ds));
+            const unsigned p = ds & 3u;
+            double v = tab.coef[T];
+            if (p >= 1) {
+                NNGP_FUNC_KEEP_BRANCH();
+                v = v * x[(ds >> 2) & 7u];
+                if (p >= 2) {
+                    NNGP_FUNC_KEEP_BRANCH();
+                    v = v * x[(ds >> 5) & 7u];
+                    if (p >= 3) {
+                        NNGP_FUNC_KEEP_BRANCH();
+                        v = v * x[(ds >> 8) & 7u];
+                    }
+                }
+            }
+            const double before = (ds & (1u << 13)) ? -0.0 : acc;   // -0.0 + v is v bit for bit
+            acc = before + v;
+            if (__builtin_expect((ds & (1u << 14)) != 0, 0)) {
+                NNGP_FUNC_KEEP_BRANCH();
+                const unsigned row = (ds >> 11) & 3u;
+#pragma unroll
+                for (int c = 0; c < D; c++)
+                    if (row == (unsigned)c) r[c] = acc;
+            }
+            func_lane_terms<D, T + 1>(tab, n, x, r, acc);
+        }
+    }
+}
+
+template <int D_> struct FuncLane {
+    static constexpr int D = D_;
+    __device__ __forceinline__ static void f(const double *u, double *o, const FuncLaneArgs &a) {
+        double x[POLY_LANE_SLOTS], r[POLY_LANE_D];
+#pragma unroll
+        for (int c = 0; c < POLY_LANE_SLOTS; c++) x[c] = c < D ? u[c] : 1.0;
+#pragma unroll
+        for (int c = 0; c < POLY_LANE_D; c++) r[c] = 0.0;   // a row without terms: +0.0
+        int na = a.tab.n_atoms, n = a.tab.n;
+        asm volatile("" : "+s"(na), "+s"(n));
+        func_lane_atoms<D, 0>(a.tab, na, x);
+        func_lane_terms<D, 0>(a.tab, n, x, r, 0.0);
+#pragma unroll
+        for (int c = 0; c < D; c++) o[c] = r[c];
+    }
+};
+#undef NNGP_FUNC_KEEP_BRANCH
+template <> struct LaneSys<NNGP_SYS_FUNC_LANE + 1> : FuncLane<1> {};
+template <> struct LaneSys<NNGP_SYS_FUNC_LANE + 2> : FuncLane<2> {};
+template <> struct LaneSys<NNGP_SYS_FUNC_LANE + 3> : FuncLane<3> {};
+template <> struct LaneSys<NNGP_SYS_FUNC_LANE + 4> : FuncLane<4> {};
+
 // f_n(u) = f(inverse(u)) * scale   (systems.py:36-40), inverse(u) = ((u+1)/2)*(mx-mn) + mn
 // (utils.py:24) evaluated as (u+1)*((mx-mn)/2) + mn: halving is exact for normal numbers, so
 // RN(RN(u+1)/2 * w) == RN(RN(u+1) * (w/2)) bit for bit, one multiply fewer per component.  NORM is a template parameter so the RK
@@ -425,11 +578,19 @@ struct FieldArgs {
             const PolyTerm *p_terms;  // DEVICE [n_terms]
         };
     };
+    // (NNGP_SYS_FUNC is a polynomial table too; its atom records lie between the terms and the row
+    // pointers of the same device block -- func_atoms_of -- and `nx` holds their count)
     double b_off, b_diag;
     // DiffReact: 1/dx^2, 1/dy^2, the main diagonal -(a)/dx^2 - (b)/dy^2 with a (b) = 2 inside a
     // row (column) and 1 at its two ends (m_ab), and Du, Dv, k
     double r_cx, r_cy, r_m22, r_m12, r_m21, r_m11, r_du, r_dv, r_k;
 };
+
+// NNGP_SYS_FUNC: the device block is terms [n_terms] | atoms [nx] | row_ptr [d+1] (nngp_func.hip),
+// and row_ptr[d] = n_terms
+__device__ __forceinline__ const nngp_func_atom *func_atoms_of(const FieldArgs &fa) {
+    return (const nngp_func_atom *)(fa.p_terms + fa.p_row[fa.d]);
+}
 
 __device__ __forceinline__ double wave_prev(double v) {   // lane i <- lane i-1 (lane 0 <- 63)
     return __builtin_amdgcn_mov_dpp(v, 0x13C, 0xF, 0xF, false);

@@ -57,6 +57,27 @@ __global__ void __launch_bounds__(64) rk_poly_lane_kernel(PolyLaneArgs args, int
                                                u0 + (size_t)i * D, uF + (size_t)i * D);
 }
 
+// The lane kernel of a field with atoms (NNGP_SYS_FUNC with d = D <= 4, at most 4 atoms and 16 terms):
+// as rk_poly_lane_kernel, on LaneSys<NNGP_SYS_FUNC_LANE + D> with its table in FuncLaneArgs.  No
+// group form either.
+template <int D, int ORDER, bool LINSPACE, bool NORM, bool TRAJ>
+__global__ void __launch_bounds__(64) rk_func_lane_kernel(FuncLaneArgs args, int n_slices,
+                                                          const double *__restrict__ t0,
+                                                          const double *__restrict__ t1, int64_t steps,
+                                                          int64_t gsteps, const int64_t *__restrict__ j0s,
+                                                          const double *__restrict__ u0,
+                                                          double *__restrict__ uF) {
+    constexpr int SYS = NNGP_SYS_FUNC_LANE + D;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_slices) return;
+    if constexpr (TRAJ)
+        lane_slice<SYS, ORDER, LINSPACE, NORM, true>(args, t0[i], t1[i], steps, steps, 0, u0 + (size_t)i * D,
+                                                     traj_block(uF, i, steps, gsteps, D), gsteps);
+    else
+        lane_slice<SYS, ORDER, LINSPACE, NORM>(args, t0[i], t1[i], steps, gsteps, j0s ? j0s[i] : 0,
+                                               u0 + (size_t)i * D, uF + (size_t)i * D);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Lane-group kernel: one slice = one group of G lanes, each component on its own lanes: G = 16
 // (components in DPP banks, below) for every ODE but Thomas labyrinth, G = 4 (lane c = component c,
@@ -1047,6 +1068,28 @@ __device__ __forceinline__ double poly_elem(const double *__restrict__ V, int b,
     return acc;
 }
 
+// the kinds whose rows are a term table in device memory (FieldArgs::p_row / p_terms)
+__host__ __device__ constexpr bool table_sys(int sys) { return sys == NNGP_SYS_POLY || sys == NNGP_SYS_FUNC; }
+
+// doubles per stage image: the state, and for NNGP_SYS_FUNC the atoms behind it
+template <int SYS>
+__host__ __device__ __forceinline__ int image_doubles(const FieldArgs &fa) {
+    if constexpr (SYS == NNGP_SYS_FUNC) return fa.d + fa.nx;   // nx: the number of atoms
+    else return fa.d;
+}
+
+// Field with atoms (NNGP_SYS_FUNC): once the state part V[0 .. d) of the image is
+// written and the stage's barrier passed, thread t evaluates atoms t, t + BT, ... from it into the
+// image's tail V[d + q]; behind a second barrier poly_elem walks the rows over the extended image.
+// Atoms read the state part only, so the two parts never race; the double buffering argument of
+// rk_field_kernel holds for the tail as for the state (the tail written in stage s was last read
+// before the second barrier of stage s - 1 ... of the other image: two barriers earlier at least).
+__device__ __forceinline__ void func_atoms_stage(double *__restrict__ V, const FieldArgs &fa,
+                                                 const nngp_func_atom *__restrict__ atoms, int tid, int BT) {
+    for (int q = tid; q < fa.nx; q += BT) V[fa.d + q] = func_atom_value(atoms[q], V);
+    __syncthreads();
+}
+
 // <= 256 threads per slice leaves ~170 VGPRs for u, the S stage vectors and the neighbour table
 template <int SYS, int ORDER, bool LINSPACE, int EPT, bool NORM, bool TRAJ>
 __global__ void __launch_bounds__(EPT == 1 ? 1024 : (EPT == 2 ? 512 : 256)) rk_field_kernel(FieldArgs fa, int n_slices,
@@ -1069,13 +1112,16 @@ __global__ void __launch_bounds__(EPT == 1 ? 1024 : (EPT == 2 ? 512 : 256)) rk_f
     int e_[EPT];
     Nbr5 nb[(SYS == NNGP_SYS_FHN_PDE) ? EPT : 1];
     DrNbr rnb[(SYS == NNGP_SYS_DIFFREACT) ? EPT : 1];
-    int pb[(SYS == NNGP_SYS_POLY) ? EPT : 1], pe[(SYS == NNGP_SYS_POLY) ? EPT : 1];   // the rows' term ranges
+    int pb[table_sys(SYS) ? EPT : 1], pe[table_sys(SYS) ? EPT : 1];   // the rows' term ranges
+    const int W = image_doubles<SYS>(fa);
+    const nngp_func_atom *fatoms = nullptr;
+    if constexpr (SYS == NNGP_SYS_FUNC) fatoms = func_atoms_of(fa);
 #pragma unroll
     for (int r = 0; r < EPT; r++) {
         const int e = tid + r * BT;
         e_[r] = e;
         const bool ok = e < d;
-        if constexpr (SYS == NNGP_SYS_POLY) {
+        if constexpr (table_sys(SYS)) {
             pb[r] = ok ? fa.p_row[e] : 0;
             pe[r] = ok ? fa.p_row[e + 1] : 0;
         }
@@ -1112,7 +1158,7 @@ __global__ void __launch_bounds__(EPT == 1 ? 1024 : (EPT == 2 ? 512 : 256)) rk_f
         const double h = LINSPACE ? grid.next(n, T0, T1, dt) : dt;
 #pragma unroll
         for (int s = 0; s < S; s++) {
-            double *V = smem + buf * d;
+            double *V = smem + buf * W;
 #pragma unroll
             for (int r = 0; r < EPT; r++) {
                 if (e_[r] < d) {
@@ -1121,6 +1167,7 @@ __global__ void __launch_bounds__(EPT == 1 ? 1024 : (EPT == 2 ? 512 : 256)) rk_f
                 }
             }
             __syncthreads();
+            if constexpr (SYS == NNGP_SYS_FUNC) func_atoms_stage(V, fa, fatoms, tid, BT);
 #pragma unroll
             for (int r = 0; r < EPT; r++) {
                 const int e = e_[r];
@@ -1130,7 +1177,7 @@ __global__ void __launch_bounds__(EPT == 1 ? 1024 : (EPT == 2 ? 512 : 256)) rk_f
                         f = burgers_elem(V, e, d, fa);
                     } else if constexpr (SYS == NNGP_SYS_DIFFREACT) {
                         f = dr_elem(V, e, half, rnb[r], fa);
-                    } else if constexpr (SYS == NNGP_SYS_POLY) {
+                    } else if constexpr (table_sys(SYS)) {
                         f = poly_elem(V, pb[r], pe[r], fa.p_terms);
                     } else {   // FHN_PDE, systems.py:365-366
                         if (e < half) {
@@ -1528,7 +1575,7 @@ template <int SYS, int ORDER, bool LIN, int EPT, bool TRAJ>
 static int launch_field_ept(const FieldArgs &fa, int bt, int n, const double *t0,
                             const double *t1, int64_t steps, int64_t gsteps, const int64_t *j0,
                             const double *u0, double *uF, hipStream_t st) {
-    const size_t lds = sizeof(double) * 2 * (size_t)fa.d;
+    const size_t lds = sizeof(double) * 2 * (size_t)image_doubles<SYS>(fa);
     if (fa.normalized)
         hipLaunchKernelGGL((rk_field_kernel<SYS, ORDER, LIN, EPT, true, TRAJ>), dim3(n), dim3(bt), lds, st, fa, n,
                            t0, t1, steps, gsteps, j0, u0, uF);
@@ -1597,6 +1644,14 @@ static int field_args(const nngp_system *sys, FieldArgs &fa) {
         // this device's first use)
         int rc = poly_device(sys, &fa.p_row, &fa.p_terms);
         if (rc) return rc;
+    } else if (sys->kind == NNGP_SYS_FUNC) {
+        FuncTable ft;
+        int rc = func_table(sys, &ft);   // host checks first, as for NNGP_SYS_POLY
+        if (rc) return rc;
+        const nngp_func_atom *atoms = nullptr;   // behind the terms in the same block: func_atoms_of
+        rc = func_device(sys, &fa.p_row, &fa.p_terms, &atoms);
+        if (rc) return rc;
+        fa.nx = ft.n_atoms;
     } else {
         NNGP_REQUIRE(sys->nx >= 3 && sys->d == 2 * sys->nx * sys->nx, "FHN_PDE needs d = 2 nx^2, nx >= 3");
         const double dx = (1.0 - (-1.0)) / (sys->nx - 1);
@@ -1607,7 +1662,8 @@ static int field_args(const nngp_system *sys, FieldArgs &fa) {
         fa.b_off = 5E-3 * c1;
         fa.b_diag = 5E-3 * ldiag;
     }
-    NNGP_REQUIRE(sizeof(double) * 2 * (size_t)sys->d <= 160 * 1024, "LDS image too large");
+    NNGP_REQUIRE(sizeof(double) * 2 * ((size_t)sys->d + (sys->kind == NNGP_SYS_FUNC ? fa.nx : 0)) <= 160 * 1024,
+                 "LDS image too large");
     return NNGP_OK;
 }
 
@@ -1739,6 +1795,72 @@ static int launch_poly(const nngp_system *sys, int n, const double *t0, const do
     }
 }
 
+// the lane form's table of a field with atoms (FuncLaneTab, nngp_rk_dev.h)
+static void func_lane_tab(const FuncTable &ft, FuncLaneTab &tab) {
+    tab = FuncLaneTab{};
+    tab.n = ft.n_terms;
+    tab.n_atoms = ft.n_atoms;
+    for (int q = 0; q < ft.n_atoms; q++) {
+        const nngp_func_atom &A = ft.atoms[q];
+        tab.a[q] = A.a;
+        tab.c[q] = A.c;
+        tab.b[q] = A.b;
+        tab.adesc[q] = (uint16_t)((unsigned)A.fn | (unsigned)A.i << 3 | (unsigned)(A.j >= 0 ? A.j : 0) << 5 |
+                                  (unsigned)(A.j >= 0) << 7 | (unsigned)(A.has_b != 0) << 8);
+    }
+    for (int c = 0; c < ft.d; c++)
+        for (int t = ft.row_ptr[c]; t < ft.row_ptr[c + 1]; t++) {
+            const PolyTerm &T = ft.terms[t];
+            const unsigned p = (T.i >= 0) + (T.j >= 0) + (T.k >= 0);
+            tab.coef[t] = T.coef;
+            tab.desc[t] = (uint16_t)(p | (unsigned)(T.i >= 0 ? T.i : 0) << 2 | (unsigned)(T.j >= 0 ? T.j : 0) << 5 |
+                                     (unsigned)(T.k >= 0 ? T.k : 0) << 8 | (unsigned)c << 11 |
+                                     (unsigned)(t == ft.row_ptr[c]) << 13 | (unsigned)(t + 1 == ft.row_ptr[c + 1]) << 14);
+        }
+}
+// whether a table takes the lane form: d <= 4, at most 4 atoms and 16 terms (so d + n_atoms <= 8
+// slots and 3-bit indices); anything larger takes the field form
+static bool func_lane_fits(const FuncTable &ft) {
+    return ft.d <= POLY_LANE_D && ft.n_atoms <= FUNC_LANE_ATOMS && ft.n_terms <= POLY_LANE_TERMS;
+}
+
+template <int D, int ORDER, bool LIN, bool TRAJ>
+static int launch_func_lane(const nngp_system *sys, const FuncTable &ft, int n, const double *t0, const double *t1,
+                            int64_t steps, int64_t gsteps, const int64_t *j0, const double *u0, double *uF,
+                            hipStream_t st) {
+    FuncLaneArgs a{};
+    a.normalized = sys->normalized;
+    a.norm = sys->norm;
+    func_lane_tab(ft, a.tab);
+    const int bs = 64;
+    if (sys->normalized)
+        hipLaunchKernelGGL((rk_func_lane_kernel<D, ORDER, LIN, true, TRAJ>), dim3((n + bs - 1) / bs), dim3(bs), 0, st,
+                           a, n, t0, t1, steps, gsteps, j0, u0, uF);
+    else
+        hipLaunchKernelGGL((rk_func_lane_kernel<D, ORDER, LIN, false, TRAJ>), dim3((n + bs - 1) / bs), dim3(bs), 0, st,
+                           a, n, t0, t1, steps, gsteps, j0, u0, uF);
+    NNGP_LAUNCH_CHECK();
+    return NNGP_OK;
+}
+
+// NNGP_SYS_FUNC: the lane form while the table fits the kernel arguments, else the field form
+template <int ORDER, bool LIN, bool TRAJ>
+static int launch_func(const nngp_system *sys, int n, const double *t0, const double *t1, int64_t steps,
+                       int64_t gsteps, const int64_t *j0, const double *u0, double *uF, hipStream_t st) {
+    FuncTable ft;
+    int rc = func_table(sys, &ft);   // host checks, before any HIP call
+    if (rc) return rc;
+    NNGP_REQUIRE(!sys->normalized || sys->norm != nullptr, "normalized system needs norm[3d]");
+    if (!func_lane_fits(ft))
+        return launch_field<NNGP_SYS_FUNC, ORDER, LIN, TRAJ>(sys, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    switch (ft.d) {
+    case 1: return launch_func_lane<1, ORDER, LIN, TRAJ>(sys, ft, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    case 2: return launch_func_lane<2, ORDER, LIN, TRAJ>(sys, ft, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    case 3: return launch_func_lane<3, ORDER, LIN, TRAJ>(sys, ft, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    default: return launch_func_lane<4, ORDER, LIN, TRAJ>(sys, ft, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    }
+}
+
 template <int ORDER, bool LIN, bool TRAJ>
 static int dispatch_sys(const nngp_system *s, int n, const double *t0, const double *t1,
                         int64_t steps, int64_t gsteps, const int64_t *j0, const double *u0,
@@ -1758,6 +1880,7 @@ static int dispatch_sys(const nngp_system *s, int n, const double *t0, const dou
     case NNGP_SYS_DIFFREACT:
         return launch_field<NNGP_SYS_DIFFREACT, ORDER, LIN, TRAJ>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
     case NNGP_SYS_POLY: return launch_poly<ORDER, LIN, TRAJ>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    case NNGP_SYS_FUNC: return launch_func<ORDER, LIN, TRAJ>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
     default: set_error("unknown system kind %d", s->kind); return NNGP_E_ARG;
     }
 }

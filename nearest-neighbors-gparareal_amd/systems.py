@@ -266,3 +266,121 @@ class PolyODE(ODE):
             self.destroy()
         except Exception:   # interpreter teardown
             pass
+
+
+class FuncODE(ODE):
+    """A user-defined system whose right-hand side is monomials over the state and over
+    elementary-function atoms of it: PolyODE with sin, cos, exp, log, 1/x and sqrt.
+
+    atoms[q] is (fn, (a, i)), (fn, (a, i), (c, j)), or either with a trailing scalar b:
+        atom_q = fn(a*u[i] + c*u[j] + b),   fn in 'sin', 'cos', 'exp', 'log', 'recip', 'sqrt'
+    the argument formed left to right, an absent part not added.  Atoms read the state only.
+    terms[c] is PolyODE's ordered list of (coef, indices) for row c, 0 to 3 indices each, where an
+    index below d names a state component and d + q names atom q.  A damped pendulum is
+        FuncODE(atoms=[('sin', (1.0, 0))], terms=[[(1.0, (1,))], [(-1.0, (2,)), (-0.1, (1,))]], u0=[1.0, 0.0])
+    normalization='-11' needs mn and mx; the atoms see the de-normalised state.  The library's table
+    (nngp_func_create) is made on the first use of the descriptor and destroyed with the object;
+    everything else is ODE's, so SolverRK, SolverScipy, Parareal, build_cont_traj and the legacy
+    solver take it like any other system."""
+    kind = _lib.SYS_FUNC
+    MAX_D, MAX_ATOMS, MAX_DEGREE = 2048, 2048, 3
+    FUNCTIONS = _lib.FUNC_FN
+
+    def __init__(self, atoms, terms, u0, mn=None, mx=None, name='FuncODE', normalization=None, **kwargs):
+        u0 = np.array(u0, dtype=float)
+        if u0.ndim != 1 or not 1 <= u0.shape[0] <= self.MAX_D:
+            raise ValueError(f'FuncODE: u0 must be a vector of 1..{self.MAX_D} components')
+        d = u0.shape[0]
+        atoms = list(atoms)
+        if len(atoms) > self.MAX_ATOMS:
+            raise ValueError(f'FuncODE: {len(atoms)} atoms (at most {self.MAX_ATOMS})')
+        if len(terms) != d:
+            raise ValueError(f'FuncODE: {len(terms)} rows of terms for d = {d}')
+        if normalization is not None and normalization.lower() == '-11':
+            if mn is None or mx is None:
+                raise ValueError("FuncODE: normalization='-11' needs mn and mx")
+            mn = np.broadcast_to(np.asarray(mn, dtype=float), (d,)).copy()
+            mx = np.broadcast_to(np.asarray(mx, dtype=float), (d,)).copy()
+        recs, canon = (_lib.CFuncAtom * max(len(atoms), 1))(), []
+        for q, atom in enumerate(atoms):
+            rec = self._atom(q, atom, d)
+            canon.append(rec)
+            fn, (a, i), second, b = rec
+            c, j = second if second is not None else (0.0, -1)
+            recs[q] = _lib.CFuncAtom(self.FUNCTIONS[fn], i, j, int(b is not None), a, c, 0.0 if b is None else b)
+        nw = d + len(atoms)
+        row_ptr, coef, idx = [0], [], []
+        for c, row in enumerate(terms):
+            for coef_t, ind in row:
+                ind = [int(i) for i in ind]
+                if len(ind) > self.MAX_DEGREE:
+                    raise ValueError(f'FuncODE: row {c} has a term of degree {len(ind)} (at most {self.MAX_DEGREE})')
+                if any(not 0 <= i < nw for i in ind):
+                    raise ValueError(f'FuncODE: row {c} has an index outside [0, d + n_atoms = {nw})')
+                if not np.isfinite(coef_t):
+                    raise ValueError(f'FuncODE: row {c} has a coefficient that is not finite')
+                coef.append(float(coef_t))
+                idx.append(ind + [-1] * (self.MAX_DEGREE - len(ind)))
+            row_ptr.append(len(coef))
+        self.atoms = canon   # (fn, (a, i), (c, j) or None, b or None)
+        self.terms = [[(float(a), tuple(int(i) for i in ind)) for a, ind in row] for row in terms]
+        self._atoms = recs
+        self._row_ptr = np.array(row_ptr, dtype=np.int32)
+        self._coef = np.array(coef, dtype=np.float64)
+        self._idx = np.array(idx, dtype=np.int16).reshape(-1, 3)
+        self._handle = None
+        super().__init__(name, mn, mx, u0, normalization=normalization, **kwargs)
+
+    @classmethod
+    def _atom(cls, q, atom, d):
+        """atom q as (fn, (a, i), (c, j) or None, b or None), or ValueError"""
+        bad = f'FuncODE: atom {q} '
+        if not isinstance(atom, (tuple, list)) or not 2 <= len(atom) <= 4:
+            raise ValueError(bad + 'must be (fn, (a, i)[, (c, j)][, b])')
+        fn, parts = atom[0], list(atom[1:])
+        if fn not in cls.FUNCTIONS:
+            raise ValueError(bad + f'names the function {fn!r} (one of {", ".join(cls.FUNCTIONS)})')
+        b = None
+        if np.isscalar(parts[-1]):
+            b = float(parts.pop())
+            if not np.isfinite(b):
+                raise ValueError(bad + 'has an offset b that is not finite')
+        if not 1 <= len(parts) <= 2:
+            raise ValueError(bad + 'must be (fn, (a, i)[, (c, j)][, b])')
+        pairs = []
+        for part in parts:
+            if not isinstance(part, (tuple, list)) or len(part) != 2:
+                raise ValueError(bad + 'has a component that is not a (coefficient, state index) pair')
+            a, i = float(part[0]), int(part[1])
+            if not np.isfinite(a):
+                raise ValueError(bad + 'has a coefficient that is not finite')
+            if not 0 <= i < d:
+                raise ValueError(bad + f'has a state index outside [0, {d}) (atoms read the state only)')
+            pairs.append((a, i))
+        return fn, pairs[0], pairs[1] if len(pairs) == 2 else None, b
+
+    @property
+    def nx(self):
+        """nngp_system.nx of this kind: the table's handle, created on first use"""
+        if self._handle is None:
+            h = ctypes.c_int32(0)
+            _lib.check(_lib.lib().nngp_func_create(
+                self.d, len(self.atoms), self._atoms, len(self._coef),
+                self._row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                self._coef.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                self._idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), ctypes.byref(h)))
+            self._handle = int(h.value)
+        return self._handle
+
+    def destroy(self):
+        """Free the library's table now (else when the object goes); descriptors made from it are
+        refused from then on."""
+        h, self._handle = getattr(self, '_handle', None), None
+        if h is not None and _lib._lib is not None:
+            _lib._lib.nngp_func_destroy(h)   # after nngp_shutdown the table is gone already: ignored
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:   # interpreter teardown
+            pass
