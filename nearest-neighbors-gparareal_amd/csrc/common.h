@@ -67,9 +67,10 @@ constexpr int N_WS_SLOTS = 12;   // slot 2: the sweep's speculation buffers; 3: 
                                 // 10 / 11: the ELM prediction's scratch / nngp_elm_hidden's partial sums (nngp_elm.hip)
 void *workspace(size_t bytes, int *err, int slot = 0);
 
-// Polynomial vector fields (NNGP_SYS_POLY): the library's registry of term tables
-// (nngp_poly.hip).  One 16-byte record per term: coef and the state indices of its up to three
-// factors in multiplication order, -1 = no factor (only after the real ones).
+// Table-backed vector fields: the library's registry of term tables (nngp_table.hip).
+// Polynomial fields (NNGP_SYS_POLY): d rows of ordered terms, one 16-byte record per
+// term -- coef and the state indices of its up to three factors in multiplication order, -1 = no
+// factor (only after the real ones).
 struct alignas(16) PolyTerm {
     double coef;
     int16_t i, j, k, pad;
@@ -78,36 +79,27 @@ constexpr int POLY_MAX_D = 2048;             // one workgroup per slice, as ever
 constexpr int POLY_MAX_TERMS = 1 << 20;
 constexpr int POLY_LANE_D = 4;               // lane form: d <= 4 and at most 16 terms in total
 constexpr int POLY_LANE_TERMS = 16;
-struct PolyTable {             // a registered table as the host holds it
-    int d, n_terms;
-    const int32_t *row_ptr;    // HOST [d+1]
-    const PolyTerm *terms;     // HOST [n_terms]
-};
-// the table of sys->nx (a handle of nngp_poly_create) after checking it against sys->d: NNGP_E_ARG
-// for an unknown or destroyed handle or another d.  Makes no HIP call.
-int poly_table(const nngp_system *sys, PolyTable *out);
-// the CURRENT device's copy of that table, uploaded on first use and kept until the handle is
-// destroyed or nngp_shutdown (so steady-state calls never allocate)
-int poly_device(const nngp_system *sys, const int32_t **row_ptr, const PolyTerm **terms);
-void poly_release();   // nngp_shutdown's part: every table, host and device
-
-// Fields with elementary-function atoms (NNGP_SYS_FUNC): the registry of
-// nngp_func.hip.  A table is the polynomial field's -- the same 16-byte term records, their indices
-// over the extended vector [u_0 .. u_{d-1}, atom_0 .. atom_{n_atoms-1}] -- and n_atoms records of
-// nngp_func_atom (include/nngp.h), which the kernels read as they were registered.
+// Fields with elementary-function atoms (NNGP_SYS_FUNC): the same term records, their
+// indices over the extended vector [u_0 .. u_{d-1}, atom_0 .. atom_{n_atoms-1}], and n_atoms records
+// of nngp_func_atom (include/nngp.h), which the kernels read as they were registered.  A polynomial
+// table is one with n_atoms = 0.
 constexpr int FUNC_MAX_ATOMS = 2048;         // with d <= 2048: a stage image [2][d + n_atoms] of 64 KB
 constexpr int FUNC_LANE_ATOMS = 4;           // lane form: d <= 4, at most 4 atoms and 16 terms
-struct FuncTable {             // a registered table as the host holds it
+struct Table {                 // a registered table of either kind as the host holds it
     int d, n_atoms, n_terms;
     const int32_t *row_ptr;         // HOST [d+1]
     const PolyTerm *terms;          // HOST [n_terms]
     const nngp_func_atom *atoms;    // HOST [n_atoms]
 };
-// as poly_table / poly_device / poly_release, for the handle of nngp_func_create in sys->nx
-int func_table(const nngp_system *sys, FuncTable *out);
-int func_device(const nngp_system *sys, const int32_t **row_ptr, const PolyTerm **terms,
-                const nngp_func_atom **atoms);
-void func_release();
+// the table of sys->nx (a handle of nngp_poly_create or nngp_func_create, by sys->kind: the two
+// handle spaces are separate) after checking it against sys->d: NNGP_E_ARG for an unknown or
+// destroyed handle or another d.  Makes no HIP call.
+int table_lookup(const nngp_system *sys, Table *out);
+// the CURRENT device's copy of that table after the same checks, uploaded on first use and kept
+// until the handle is destroyed or nngp_shutdown (so steady-state calls never allocate): one block
+// terms | atoms | row_ptr, the atoms found from the other two (func_atoms_of, nngp_rk_dev.h)
+int table_device(const nngp_system *sys, const int32_t **row_ptr, const PolyTerm **terms, int *n_atoms);
+void table_release();   // nngp_shutdown's part: every table of both kinds, host and device
 
 // A prepared coordinate of gp_pre_kernel: alpha rows 0..maxm-1 | c | psy | ok
 __host__ __device__ constexpr int HM_STRIDE(int maxm) { return maxm + 3; }

@@ -105,13 +105,11 @@ static void ws_release() {
 extern "C" int nngp_shutdown(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-        nngp::poly_release();   // host tables only: nothing was uploaded
-        nngp::func_release();
+        nngp::table_release();   // host tables only: nothing was uploaded
         return NNGP_OK;
     }
     (void)hipDeviceSynchronize();
-    nngp::poly_release();
-    nngp::func_release();
+    nngp::table_release();
     nngp::chain_release();
     nngp::sweep_release();
     nngp::comm_release();

@@ -616,68 +616,44 @@ static int adapt_field(const nngp_system *sys, const AdArgs &a, hipStream_t st) 
     return adapt_field_ept<SYS, METHOD, 4>(fa, bt, a, st);
 }
 
-template <int D, int METHOD>
-static int adapt_poly_lane(const nngp_system *sys, const PolyTable &pt, const AdArgs &a, hipStream_t st) {
-    PolyLaneArgs la{};
+template <int KIND, int D, int METHOD, bool NORM>
+static auto adapt_table_lane_kernel() {
+    if constexpr (KIND == NNGP_SYS_POLY) return &rk_adapt_poly_lane_kernel<D, METHOD, NORM>;
+    else return &rk_adapt_func_lane_kernel<D, METHOD, NORM>;
+}
+
+template <int KIND, int D, int METHOD>
+static int adapt_table_lane(const nngp_system *sys, const Table &tb, const AdArgs &a, hipStream_t st) {
+    TableLaneArgs<KIND> la{};
     la.normalized = sys->normalized;
     la.norm = sys->norm;
-    poly_lane_tab(pt, la.tab);
+    lane_tab(tb, la.tab);
     const dim3 grid((a.n_slices + 63) / 64);
     if (sys->normalized)
-        hipLaunchKernelGGL((rk_adapt_poly_lane_kernel<D, METHOD, true>), grid, dim3(64), 0, st, la, a);
+        hipLaunchKernelGGL((adapt_table_lane_kernel<KIND, D, METHOD, true>()), grid, dim3(64), 0, st, la, a);
     else
-        hipLaunchKernelGGL((rk_adapt_poly_lane_kernel<D, METHOD, false>), grid, dim3(64), 0, st, la, a);
+        hipLaunchKernelGGL((adapt_table_lane_kernel<KIND, D, METHOD, false>()), grid, dim3(64), 0, st, la, a);
     NNGP_LAUNCH_CHECK();
     return NNGP_OK;
 }
 
-// the lane form while the table fits the kernel arguments, else the field form (launch_poly)
-template <int METHOD>
-static int adapt_poly(const nngp_system *sys, const PolyTable &pt, const AdArgs &a, hipStream_t st) {
+// NNGP_SYS_POLY / NNGP_SYS_FUNC: the lane form while the table fits the kernel arguments, else the
+// field form (launch_table); tb is the table nngp_rk_adaptive looked up
+template <int KIND, int METHOD>
+static int adapt_table(const nngp_system *sys, const Table &tb, const AdArgs &a, hipStream_t st) {
     NNGP_REQUIRE(!sys->normalized || sys->norm != nullptr, "normalized system needs norm[3d]");
-    if (pt.d > POLY_LANE_D || pt.n_terms > POLY_LANE_TERMS) return adapt_field<NNGP_SYS_POLY, METHOD>(sys, a, st);
-    switch (pt.d) {
-    case 1: return adapt_poly_lane<1, METHOD>(sys, pt, a, st);
-    case 2: return adapt_poly_lane<2, METHOD>(sys, pt, a, st);
-    case 3: return adapt_poly_lane<3, METHOD>(sys, pt, a, st);
-    default: return adapt_poly_lane<4, METHOD>(sys, pt, a, st);
+    if (!lane_fits(tb)) return adapt_field<KIND, METHOD>(sys, a, st);
+    switch (tb.d) {
+    case 1: return adapt_table_lane<KIND, 1, METHOD>(sys, tb, a, st);
+    case 2: return adapt_table_lane<KIND, 2, METHOD>(sys, tb, a, st);
+    case 3: return adapt_table_lane<KIND, 3, METHOD>(sys, tb, a, st);
+    default: return adapt_table_lane<KIND, 4, METHOD>(sys, tb, a, st);
     }
 }
 
-template <int D, int METHOD>
-static int adapt_func_lane(const nngp_system *sys, const FuncTable &ft, const AdArgs &a, hipStream_t st) {
-    FuncLaneArgs la{};
-    la.normalized = sys->normalized;
-    la.norm = sys->norm;
-    func_lane_tab(ft, la.tab);
-    const dim3 grid((a.n_slices + 63) / 64);
-    if (sys->normalized)
-        hipLaunchKernelGGL((rk_adapt_func_lane_kernel<D, METHOD, true>), grid, dim3(64), 0, st, la, a);
-    else
-        hipLaunchKernelGGL((rk_adapt_func_lane_kernel<D, METHOD, false>), grid, dim3(64), 0, st, la, a);
-    NNGP_LAUNCH_CHECK();
-    return NNGP_OK;
-}
-
-// NNGP_SYS_FUNC: the lane form while the table fits the kernel arguments, else the field form
-// (launch_func); the handle and d were checked by nngp_rk_adaptive
+// tb: the table of a table-backed kind, unused by the others
 template <int METHOD>
-static int adapt_func(const nngp_system *sys, const AdArgs &a, hipStream_t st) {
-    FuncTable ft;
-    int rc = func_table(sys, &ft);
-    if (rc) return rc;
-    NNGP_REQUIRE(!sys->normalized || sys->norm != nullptr, "normalized system needs norm[3d]");
-    if (!func_lane_fits(ft)) return adapt_field<NNGP_SYS_FUNC, METHOD>(sys, a, st);
-    switch (ft.d) {
-    case 1: return adapt_func_lane<1, METHOD>(sys, ft, a, st);
-    case 2: return adapt_func_lane<2, METHOD>(sys, ft, a, st);
-    case 3: return adapt_func_lane<3, METHOD>(sys, ft, a, st);
-    default: return adapt_func_lane<4, METHOD>(sys, ft, a, st);
-    }
-}
-
-template <int METHOD>
-static int adapt_sys(const nngp_system *s, const PolyTable &pt, const AdArgs &a, hipStream_t st) {
+static int adapt_sys(const nngp_system *s, const Table &tb, const AdArgs &a, hipStream_t st) {
     switch (s->kind) {
     case NNGP_SYS_LORENZ: return adapt_lane<NNGP_SYS_LORENZ, METHOD>(s, a, st);
     case NNGP_SYS_HOPF: return adapt_lane<NNGP_SYS_HOPF, METHOD>(s, a, st);
@@ -689,8 +665,8 @@ static int adapt_sys(const nngp_system *s, const PolyTable &pt, const AdArgs &a,
     case NNGP_SYS_BURGERS: return adapt_field<NNGP_SYS_BURGERS, METHOD>(s, a, st);
     case NNGP_SYS_FHN_PDE: return adapt_field<NNGP_SYS_FHN_PDE, METHOD>(s, a, st);
     case NNGP_SYS_DIFFREACT: return adapt_field<NNGP_SYS_DIFFREACT, METHOD>(s, a, st);
-    case NNGP_SYS_POLY: return adapt_poly<METHOD>(s, pt, a, st);
-    case NNGP_SYS_FUNC: return adapt_func<METHOD>(s, a, st);
+    case NNGP_SYS_POLY: return adapt_table<NNGP_SYS_POLY, METHOD>(s, tb, a, st);
+    case NNGP_SYS_FUNC: return adapt_table<NNGP_SYS_FUNC, METHOD>(s, tb, a, st);
     default: set_error("unknown system kind %d", s->kind); return NNGP_E_ARG;
     }
 }
@@ -714,20 +690,15 @@ extern "C" int nngp_rk_adaptive(const nngp_system *sys, int method, int n_slices
     NNGP_REQUIRE(std::isfinite(first_step) && first_step >= 0, "first_step must be finite and >= 0, 0 = choose "
                  "(got %g)", first_step);
     NNGP_REQUIRE(max_attempts >= 1, "max_attempts must be >= 1 (got %lld)", (long long)max_attempts);
-    PolyTable pt{};
-    if (sys->kind == NNGP_SYS_POLY) {
-        int rc = poly_table(sys, &pt);   // an unknown or destroyed handle, or another d
-        if (rc) return rc;
-    }
-    if (sys->kind == NNGP_SYS_FUNC) {
-        FuncTable ft{};
-        int rc = func_table(sys, &ft);
+    Table tb{};
+    if (table_sys(sys->kind)) {
+        int rc = table_lookup(sys, &tb);   // an unknown or destroyed handle, or another d
         if (rc) return rc;
     }
     if (n_slices == 0) return NNGP_OK;
     NNGP_REQUIRE(t0 && t1 && u0 && uF, "null array argument");
     const AdArgs a{n_slices, t0, t1, nf, rtol, atol, first_step, max_attempts, u0, uF, stats};
     hipStream_t st = (hipStream_t)stream;
-    if (method == NNGP_RK23) return adapt_sys<NNGP_RK23>(sys, pt, a, st);
-    return adapt_sys<NNGP_RK45>(sys, pt, a, st);
+    if (method == NNGP_RK23) return adapt_sys<NNGP_RK23>(sys, tb, a, st);
+    return adapt_sys<NNGP_RK45>(sys, tb, a, st);
 }

@@ -586,7 +586,7 @@ struct FieldArgs {
     double r_cx, r_cy, r_m22, r_m12, r_m21, r_m11, r_du, r_dv, r_k;
 };
 
-// NNGP_SYS_FUNC: the device block is terms [n_terms] | atoms [nx] | row_ptr [d+1] (nngp_func.hip),
+// NNGP_SYS_FUNC: the device block is terms [n_terms] | atoms [nx] | row_ptr [d+1] (nngp_table.hip),
 // and row_ptr[d] = n_terms
 __device__ __forceinline__ const nngp_func_atom *func_atoms_of(const FieldArgs &fa) {
     return (const nngp_func_atom *)(fa.p_terms + fa.p_row[fa.d]);

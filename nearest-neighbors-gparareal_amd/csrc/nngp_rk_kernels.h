@@ -1612,6 +1612,7 @@ static int field_args(const nngp_system *sys, FieldArgs &fa) {
     fa.nx = sys->nx;
     fa.normalized = sys->normalized;
     fa.norm = sys->norm;
+    int n_atoms = 0;   // of a table; behind the state in the stage image
     NNGP_REQUIRE(!sys->normalized || sys->norm, "normalized system needs norm[3d]");
     if (sys->kind == NNGP_SYS_BURGERS) {
         NNGP_REQUIRE(sys->nx == sys->d && sys->d >= 3, "Burgers needs nx == d >= 3");
@@ -1639,19 +1640,14 @@ static int field_args(const nngp_system *sys, FieldArgs &fa) {
         fa.r_du = sys->param[0];
         fa.r_dv = sys->param[1];
         fa.r_k = sys->param[2];
-    } else if (sys->kind == NNGP_SYS_POLY) {
+    } else if (table_sys(sys->kind)) {
         // the handle and d are checked on the host first; only then the device copy (uploaded on
-        // this device's first use)
-        int rc = poly_device(sys, &fa.p_row, &fa.p_terms);
+        // this device's first use).  The atoms lie behind the terms in the same block: func_atoms_of
+        int rc = table_device(sys, &fa.p_row, &fa.p_terms, &n_atoms);
         if (rc) return rc;
-    } else if (sys->kind == NNGP_SYS_FUNC) {
-        FuncTable ft;
-        int rc = func_table(sys, &ft);   // host checks first, as for NNGP_SYS_POLY
-        if (rc) return rc;
-        const nngp_func_atom *atoms = nullptr;   // behind the terms in the same block: func_atoms_of
-        rc = func_device(sys, &fa.p_row, &fa.p_terms, &atoms);
-        if (rc) return rc;
-        fa.nx = ft.n_atoms;
+        // the kernels of NNGP_SYS_FUNC read the number of atoms here; those of NNGP_SYS_POLY read
+        // nothing, and their argument block keeps the handle it has always carried
+        if (sys->kind == NNGP_SYS_FUNC) fa.nx = n_atoms;
     } else {
         NNGP_REQUIRE(sys->nx >= 3 && sys->d == 2 * sys->nx * sys->nx, "FHN_PDE needs d = 2 nx^2, nx >= 3");
         const double dx = (1.0 - (-1.0)) / (sys->nx - 1);
@@ -1662,8 +1658,7 @@ static int field_args(const nngp_system *sys, FieldArgs &fa) {
         fa.b_off = 5E-3 * c1;
         fa.b_diag = 5E-3 * ldiag;
     }
-    NNGP_REQUIRE(sizeof(double) * 2 * ((size_t)sys->d + (sys->kind == NNGP_SYS_FUNC ? fa.nx : 0)) <= 160 * 1024,
-                 "LDS image too large");
+    NNGP_REQUIRE(sizeof(double) * 2 * ((size_t)sys->d + n_atoms) <= 160 * 1024, "LDS image too large");
     return NNGP_OK;
 }
 
@@ -1742,122 +1737,88 @@ static int launch_field(const nngp_system *sys, int n, const double *t0, const d
     return launch_field_ept<SYS, ORDER, LIN, 8, TRAJ>(fa, bt, n, t0, t1, steps, gsteps, j0, u0, uF, st);
 }
 
-// the lane form's descriptor of one term (PolyLaneTab, nngp_rk_dev.h)
-static void poly_lane_tab(const PolyTable &pt, PolyLaneTab &tab) {
-    tab = PolyLaneTab{};
-    tab.n = pt.n_terms;
-    for (int c = 0; c < pt.d; c++)
-        for (int t = pt.row_ptr[c]; t < pt.row_ptr[c + 1]; t++) {
-            const PolyTerm &T = pt.terms[t];
+// The lane form of the table-backed kinds (NNGP_SYS_POLY, NNGP_SYS_FUNC): the table by value in the
+// kernel arguments, built here from the registered one.
+// the descriptors of the terms, the same bits in PolyLaneTab and FuncLaneTab (nngp_rk_dev.h; the
+// indices of a table with atoms reach 7 and take the third bit its layout leaves them)
+static void lane_terms(const Table &tb, double *coef, uint16_t *desc) {
+    for (int c = 0; c < tb.d; c++)
+        for (int t = tb.row_ptr[c]; t < tb.row_ptr[c + 1]; t++) {
+            const PolyTerm &T = tb.terms[t];
             const unsigned p = (T.i >= 0) + (T.j >= 0) + (T.k >= 0);
-            tab.coef[t] = T.coef;
-            tab.desc[t] = (uint16_t)(p | (unsigned)(T.i >= 0 ? T.i : 0) << 2 | (unsigned)(T.j >= 0 ? T.j : 0) << 5 |
-                                     (unsigned)(T.k >= 0 ? T.k : 0) << 8 | (unsigned)c << 11 |
-                                     (unsigned)(t == pt.row_ptr[c]) << 13 | (unsigned)(t + 1 == pt.row_ptr[c + 1]) << 14);
+            coef[t] = T.coef;
+            desc[t] = (uint16_t)(p | (unsigned)(T.i >= 0 ? T.i : 0) << 2 | (unsigned)(T.j >= 0 ? T.j : 0) << 5 |
+                                 (unsigned)(T.k >= 0 ? T.k : 0) << 8 | (unsigned)c << 11 |
+                                 (unsigned)(t == tb.row_ptr[c]) << 13 | (unsigned)(t + 1 == tb.row_ptr[c + 1]) << 14);
         }
 }
-
-template <int D, int ORDER, bool LIN, bool TRAJ>
-static int launch_poly_lane(const nngp_system *sys, const PolyTable &pt, int n, const double *t0, const double *t1,
-                            int64_t steps, int64_t gsteps, const int64_t *j0, const double *u0, double *uF,
-                            hipStream_t st) {
-    PolyLaneArgs a{};
-    a.normalized = sys->normalized;
-    a.norm = sys->norm;
-    poly_lane_tab(pt, a.tab);
-    const int bs = 64;
-    if (sys->normalized)
-        hipLaunchKernelGGL((rk_poly_lane_kernel<D, ORDER, LIN, true, TRAJ>), dim3((n + bs - 1) / bs), dim3(bs), 0, st,
-                           a, n, t0, t1, steps, gsteps, j0, u0, uF);
-    else
-        hipLaunchKernelGGL((rk_poly_lane_kernel<D, ORDER, LIN, false, TRAJ>), dim3((n + bs - 1) / bs), dim3(bs), 0, st,
-                           a, n, t0, t1, steps, gsteps, j0, u0, uF);
-    NNGP_LAUNCH_CHECK();
-    return NNGP_OK;
+static void lane_tab(const Table &tb, PolyLaneTab &tab) {
+    tab = PolyLaneTab{};
+    tab.n = tb.n_terms;
+    lane_terms(tb, tab.coef, tab.desc);
 }
-
-// NNGP_SYS_POLY: the lane form while the table fits the kernel arguments (d <= 4 and at most 16
-// terms), else the field form (one workgroup per slice, the table in device memory)
-template <int ORDER, bool LIN, bool TRAJ>
-static int launch_poly(const nngp_system *sys, int n, const double *t0, const double *t1, int64_t steps,
-                       int64_t gsteps, const int64_t *j0, const double *u0, double *uF, hipStream_t st) {
-    PolyTable pt;
-    int rc = poly_table(sys, &pt);   // host checks, before any HIP call
-    if (rc) return rc;
-    NNGP_REQUIRE(!sys->normalized || sys->norm != nullptr, "normalized system needs norm[3d]");
-    if (pt.d > POLY_LANE_D || pt.n_terms > POLY_LANE_TERMS)
-        return launch_field<NNGP_SYS_POLY, ORDER, LIN, TRAJ>(sys, n, t0, t1, steps, gsteps, j0, u0, uF, st);
-    switch (pt.d) {
-    case 1: return launch_poly_lane<1, ORDER, LIN, TRAJ>(sys, pt, n, t0, t1, steps, gsteps, j0, u0, uF, st);
-    case 2: return launch_poly_lane<2, ORDER, LIN, TRAJ>(sys, pt, n, t0, t1, steps, gsteps, j0, u0, uF, st);
-    case 3: return launch_poly_lane<3, ORDER, LIN, TRAJ>(sys, pt, n, t0, t1, steps, gsteps, j0, u0, uF, st);
-    default: return launch_poly_lane<4, ORDER, LIN, TRAJ>(sys, pt, n, t0, t1, steps, gsteps, j0, u0, uF, st);
-    }
-}
-
-// the lane form's table of a field with atoms (FuncLaneTab, nngp_rk_dev.h)
-static void func_lane_tab(const FuncTable &ft, FuncLaneTab &tab) {
+static void lane_tab(const Table &tb, FuncLaneTab &tab) {
     tab = FuncLaneTab{};
-    tab.n = ft.n_terms;
-    tab.n_atoms = ft.n_atoms;
-    for (int q = 0; q < ft.n_atoms; q++) {
-        const nngp_func_atom &A = ft.atoms[q];
+    tab.n = tb.n_terms;
+    tab.n_atoms = tb.n_atoms;
+    for (int q = 0; q < tb.n_atoms; q++) {
+        const nngp_func_atom &A = tb.atoms[q];
         tab.a[q] = A.a;
         tab.c[q] = A.c;
         tab.b[q] = A.b;
         tab.adesc[q] = (uint16_t)((unsigned)A.fn | (unsigned)A.i << 3 | (unsigned)(A.j >= 0 ? A.j : 0) << 5 |
                                   (unsigned)(A.j >= 0) << 7 | (unsigned)(A.has_b != 0) << 8);
     }
-    for (int c = 0; c < ft.d; c++)
-        for (int t = ft.row_ptr[c]; t < ft.row_ptr[c + 1]; t++) {
-            const PolyTerm &T = ft.terms[t];
-            const unsigned p = (T.i >= 0) + (T.j >= 0) + (T.k >= 0);
-            tab.coef[t] = T.coef;
-            tab.desc[t] = (uint16_t)(p | (unsigned)(T.i >= 0 ? T.i : 0) << 2 | (unsigned)(T.j >= 0 ? T.j : 0) << 5 |
-                                     (unsigned)(T.k >= 0 ? T.k : 0) << 8 | (unsigned)c << 11 |
-                                     (unsigned)(t == ft.row_ptr[c]) << 13 | (unsigned)(t + 1 == ft.row_ptr[c + 1]) << 14);
-        }
+    lane_terms(tb, tab.coef, tab.desc);
 }
-// whether a table takes the lane form: d <= 4, at most 4 atoms and 16 terms (so d + n_atoms <= 8
-// slots and 3-bit indices); anything larger takes the field form
-static bool func_lane_fits(const FuncTable &ft) {
-    return ft.d <= POLY_LANE_D && ft.n_atoms <= FUNC_LANE_ATOMS && ft.n_terms <= POLY_LANE_TERMS;
+// whether a table takes the lane form: d <= 4, at most 16 terms and at most 4 atoms (so d + n_atoms
+// <= 8 slots and 3-bit indices; a polynomial table has none); anything larger takes the field form
+// (one workgroup per slice, the table in device memory)
+static bool lane_fits(const Table &tb) {
+    return tb.d <= POLY_LANE_D && tb.n_atoms <= FUNC_LANE_ATOMS && tb.n_terms <= POLY_LANE_TERMS;
+}
+// what KIND (NNGP_SYS_POLY or NNGP_SYS_FUNC) selects: the argument type and the kernel
+template <int KIND> using TableLaneArgs = std::conditional_t<KIND == NNGP_SYS_POLY, PolyLaneArgs, FuncLaneArgs>;
+template <int KIND, int D, int ORDER, bool LIN, bool NORM, bool TRAJ>
+static auto table_lane_kernel() {
+    if constexpr (KIND == NNGP_SYS_POLY) return &rk_poly_lane_kernel<D, ORDER, LIN, NORM, TRAJ>;
+    else return &rk_func_lane_kernel<D, ORDER, LIN, NORM, TRAJ>;
 }
 
-template <int D, int ORDER, bool LIN, bool TRAJ>
-static int launch_func_lane(const nngp_system *sys, const FuncTable &ft, int n, const double *t0, const double *t1,
-                            int64_t steps, int64_t gsteps, const int64_t *j0, const double *u0, double *uF,
-                            hipStream_t st) {
-    FuncLaneArgs a{};
+template <int KIND, int D, int ORDER, bool LIN, bool TRAJ>
+static int launch_table_lane(const nngp_system *sys, const Table &tb, int n, const double *t0, const double *t1,
+                             int64_t steps, int64_t gsteps, const int64_t *j0, const double *u0, double *uF,
+                             hipStream_t st) {
+    TableLaneArgs<KIND> a{};
     a.normalized = sys->normalized;
     a.norm = sys->norm;
-    func_lane_tab(ft, a.tab);
+    lane_tab(tb, a.tab);
     const int bs = 64;
     if (sys->normalized)
-        hipLaunchKernelGGL((rk_func_lane_kernel<D, ORDER, LIN, true, TRAJ>), dim3((n + bs - 1) / bs), dim3(bs), 0, st,
-                           a, n, t0, t1, steps, gsteps, j0, u0, uF);
+        hipLaunchKernelGGL((table_lane_kernel<KIND, D, ORDER, LIN, true, TRAJ>()), dim3((n + bs - 1) / bs), dim3(bs), 0,
+                           st, a, n, t0, t1, steps, gsteps, j0, u0, uF);
     else
-        hipLaunchKernelGGL((rk_func_lane_kernel<D, ORDER, LIN, false, TRAJ>), dim3((n + bs - 1) / bs), dim3(bs), 0, st,
-                           a, n, t0, t1, steps, gsteps, j0, u0, uF);
+        hipLaunchKernelGGL((table_lane_kernel<KIND, D, ORDER, LIN, false, TRAJ>()), dim3((n + bs - 1) / bs), dim3(bs), 0,
+                           st, a, n, t0, t1, steps, gsteps, j0, u0, uF);
     NNGP_LAUNCH_CHECK();
     return NNGP_OK;
 }
 
-// NNGP_SYS_FUNC: the lane form while the table fits the kernel arguments, else the field form
-template <int ORDER, bool LIN, bool TRAJ>
-static int launch_func(const nngp_system *sys, int n, const double *t0, const double *t1, int64_t steps,
-                       int64_t gsteps, const int64_t *j0, const double *u0, double *uF, hipStream_t st) {
-    FuncTable ft;
-    int rc = func_table(sys, &ft);   // host checks, before any HIP call
+// NNGP_SYS_POLY / NNGP_SYS_FUNC: the lane form while the table fits the kernel arguments, else the
+// field form
+template <int KIND, int ORDER, bool LIN, bool TRAJ>
+static int launch_table(const nngp_system *sys, int n, const double *t0, const double *t1, int64_t steps,
+                        int64_t gsteps, const int64_t *j0, const double *u0, double *uF, hipStream_t st) {
+    Table tb;
+    int rc = table_lookup(sys, &tb);   // host checks, before any HIP call
     if (rc) return rc;
     NNGP_REQUIRE(!sys->normalized || sys->norm != nullptr, "normalized system needs norm[3d]");
-    if (!func_lane_fits(ft))
-        return launch_field<NNGP_SYS_FUNC, ORDER, LIN, TRAJ>(sys, n, t0, t1, steps, gsteps, j0, u0, uF, st);
-    switch (ft.d) {
-    case 1: return launch_func_lane<1, ORDER, LIN, TRAJ>(sys, ft, n, t0, t1, steps, gsteps, j0, u0, uF, st);
-    case 2: return launch_func_lane<2, ORDER, LIN, TRAJ>(sys, ft, n, t0, t1, steps, gsteps, j0, u0, uF, st);
-    case 3: return launch_func_lane<3, ORDER, LIN, TRAJ>(sys, ft, n, t0, t1, steps, gsteps, j0, u0, uF, st);
-    default: return launch_func_lane<4, ORDER, LIN, TRAJ>(sys, ft, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    if (!lane_fits(tb)) return launch_field<KIND, ORDER, LIN, TRAJ>(sys, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    switch (tb.d) {
+    case 1: return launch_table_lane<KIND, 1, ORDER, LIN, TRAJ>(sys, tb, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    case 2: return launch_table_lane<KIND, 2, ORDER, LIN, TRAJ>(sys, tb, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    case 3: return launch_table_lane<KIND, 3, ORDER, LIN, TRAJ>(sys, tb, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    default: return launch_table_lane<KIND, 4, ORDER, LIN, TRAJ>(sys, tb, n, t0, t1, steps, gsteps, j0, u0, uF, st);
     }
 }
 
@@ -1879,8 +1840,8 @@ static int dispatch_sys(const nngp_system *s, int n, const double *t0, const dou
     case NNGP_SYS_FHN_PDE: return launch_field<NNGP_SYS_FHN_PDE, ORDER, LIN, TRAJ>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
     case NNGP_SYS_DIFFREACT:
         return launch_field<NNGP_SYS_DIFFREACT, ORDER, LIN, TRAJ>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
-    case NNGP_SYS_POLY: return launch_poly<ORDER, LIN, TRAJ>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
-    case NNGP_SYS_FUNC: return launch_func<ORDER, LIN, TRAJ>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    case NNGP_SYS_POLY: return launch_table<NNGP_SYS_POLY, ORDER, LIN, TRAJ>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
+    case NNGP_SYS_FUNC: return launch_table<NNGP_SYS_FUNC, ORDER, LIN, TRAJ>(s, n, t0, t1, steps, gsteps, j0, u0, uF, st);
     default: set_error("unknown system kind %d", s->kind); return NNGP_E_ARG;
     }
 }

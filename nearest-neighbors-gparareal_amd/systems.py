@@ -195,7 +195,86 @@ class DiffReact(ODE):
         super().__init__(f'DiffReact2D_{d_x}', mn, mx, u0, param=(float(Du), float(Dv), float(k)), **kwargs)
 
 
-class PolyODE(ODE):
+class _TableODE(ODE):
+    """What the table-backed systems (PolyODE, FuncODE) share: the checks of u0, mn and mx, the packing
+    of the rows of terms, and the library's table -- made on the first use of the descriptor, destroyed
+    with the object.  A subclass sets LABEL (the prefix of its messages) and DESTROY (the library's
+    destroy entry point) and has _create(handle_ref), the call of its create entry point."""
+    MAX_D, MAX_DEGREE = 2048, 3
+    LABEL = DESTROY = None
+
+    @classmethod
+    def _state(cls, u0):
+        """u0 as a float vector, and d"""
+        u0 = np.array(u0, dtype=float)
+        if u0.ndim != 1 or not 1 <= u0.shape[0] <= cls.MAX_D:
+            raise ValueError(f'{cls.LABEL}: u0 must be a vector of 1..{cls.MAX_D} components')
+        return u0, u0.shape[0]
+
+    @classmethod
+    def _bounds(cls, terms, d, mn, mx, normalization):
+        """mn and mx as the normaliser takes them, after the check of the number of rows"""
+        if len(terms) != d:
+            raise ValueError(f'{cls.LABEL}: {len(terms)} rows of terms for d = {d}')
+        if normalization is not None and normalization.lower() == '-11':
+            if mn is None or mx is None:
+                raise ValueError(f"{cls.LABEL}: normalization='-11' needs mn and mx")
+            mn = np.broadcast_to(np.asarray(mn, dtype=float), (d,)).copy()
+            mx = np.broadcast_to(np.asarray(mx, dtype=float), (d,)).copy()
+        return mn, mx
+
+    def _pack_terms(self, terms, bound, interval):
+        """self.terms and the library's arrays of them; the indices lie in [0, bound), which the
+        message calls `interval`"""
+        row_ptr, coef, idx = [0], [], []
+        for c, row in enumerate(terms):
+            for coef_t, ind in row:
+                ind = [int(i) for i in ind]
+                if len(ind) > self.MAX_DEGREE:
+                    raise ValueError(f'{self.LABEL}: row {c} has a term of degree {len(ind)} (at most {self.MAX_DEGREE})')
+                if any(not 0 <= i < bound for i in ind):
+                    raise ValueError(f'{self.LABEL}: row {c} has an index outside {interval}')
+                if not np.isfinite(coef_t):
+                    raise ValueError(f'{self.LABEL}: row {c} has a coefficient that is not finite')
+                coef.append(float(coef_t))
+                idx.append(ind + [-1] * (self.MAX_DEGREE - len(ind)))
+            row_ptr.append(len(coef))
+        self.terms = [[(float(a), tuple(int(i) for i in ind)) for a, ind in row] for row in terms]
+        self._row_ptr = np.array(row_ptr, dtype=np.int32)
+        self._coef = np.array(coef, dtype=np.float64)
+        self._idx = np.array(idx, dtype=np.int16).reshape(-1, 3)
+        self._handle = None
+
+    def _term_args(self):
+        """n_terms, row_ptr, coef, idx as the create entry points take them"""
+        return (len(self._coef), self._row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                self._coef.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                self._idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)))
+
+    @property
+    def nx(self):
+        """nngp_system.nx of this kind: the table's handle, created on first use"""
+        if self._handle is None:
+            h = ctypes.c_int32(0)
+            _lib.check(self._create(ctypes.byref(h)))
+            self._handle = int(h.value)
+        return self._handle
+
+    def destroy(self):
+        """Free the library's table now (else when the object goes); descriptors made from it are
+        refused from then on."""
+        h, self._handle = getattr(self, '_handle', None), None
+        if h is not None and _lib._lib is not None:
+            getattr(_lib._lib, self.DESTROY)(h)   # after nngp_shutdown the table is gone already: ignored
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:   # interpreter teardown
+            pass
+
+
+class PolyODE(_TableODE):
     """A user-defined polynomial system: the counterpart of subclassing the reference's ODE and
     writing _f_np / _f_jax (systems.py:23-61), with the right-hand side given as data.
 
@@ -209,66 +288,19 @@ class PolyODE(ODE):
     SolverRK, Parareal, build_cont_traj and the legacy solver take it like any other system."""
     kind = _lib.SYS_POLY
     MAX_D, MAX_DEGREE = 2048, 3
+    LABEL, DESTROY = 'PolyODE', 'nngp_poly_destroy'
 
     def __init__(self, terms, u0, mn=None, mx=None, name='PolyODE', normalization=None, **kwargs):
-        u0 = np.array(u0, dtype=float)
-        if u0.ndim != 1 or not 1 <= u0.shape[0] <= self.MAX_D:
-            raise ValueError(f'PolyODE: u0 must be a vector of 1..{self.MAX_D} components')
-        d = u0.shape[0]
-        if len(terms) != d:
-            raise ValueError(f'PolyODE: {len(terms)} rows of terms for d = {d}')
-        if normalization is not None and normalization.lower() == '-11':
-            if mn is None or mx is None:
-                raise ValueError("PolyODE: normalization='-11' needs mn and mx")
-            mn = np.broadcast_to(np.asarray(mn, dtype=float), (d,)).copy()
-            mx = np.broadcast_to(np.asarray(mx, dtype=float), (d,)).copy()
-        row_ptr, coef, idx = [0], [], []
-        for c, row in enumerate(terms):
-            for coef_t, ind in row:
-                ind = [int(i) for i in ind]
-                if len(ind) > self.MAX_DEGREE:
-                    raise ValueError(f'PolyODE: row {c} has a term of degree {len(ind)} (at most {self.MAX_DEGREE})')
-                if any(not 0 <= i < d for i in ind):
-                    raise ValueError(f'PolyODE: row {c} has an index outside [0, {d})')
-                if not np.isfinite(coef_t):
-                    raise ValueError(f'PolyODE: row {c} has a coefficient that is not finite')
-                coef.append(float(coef_t))
-                idx.append(ind + [-1] * (self.MAX_DEGREE - len(ind)))
-            row_ptr.append(len(coef))
-        self.terms = [[(float(a), tuple(int(i) for i in ind)) for a, ind in row] for row in terms]
-        self._row_ptr = np.array(row_ptr, dtype=np.int32)
-        self._coef = np.array(coef, dtype=np.float64)
-        self._idx = np.array(idx, dtype=np.int16).reshape(-1, 3)
-        self._handle = None
+        u0, d = self._state(u0)
+        mn, mx = self._bounds(terms, d, mn, mx, normalization)
+        self._pack_terms(terms, d, f'[0, {d})')
         super().__init__(name, mn, mx, u0, normalization=normalization, **kwargs)
 
-    @property
-    def nx(self):
-        """nngp_system.nx of this kind: the table's handle, created on first use"""
-        if self._handle is None:
-            h = ctypes.c_int32(0)
-            _lib.check(_lib.lib().nngp_poly_create(
-                self.d, len(self._coef), self._row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                self._coef.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                self._idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), ctypes.byref(h)))
-            self._handle = int(h.value)
-        return self._handle
-
-    def destroy(self):
-        """Free the library's table now (else when the object goes); descriptors made from it are
-        refused from then on."""
-        h, self._handle = getattr(self, '_handle', None), None
-        if h is not None and _lib._lib is not None:
-            _lib._lib.nngp_poly_destroy(h)   # after nngp_shutdown the table is gone already: ignored
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:   # interpreter teardown
-            pass
+    def _create(self, handle_ref):
+        return _lib.lib().nngp_poly_create(self.d, *self._term_args(), handle_ref)
 
 
-class FuncODE(ODE):
+class FuncODE(_TableODE):
     """A user-defined system whose right-hand side is monomials over the state and over
     elementary-function atoms of it: PolyODE with sin, cos, exp, log, 1/x and sqrt.
 
@@ -285,22 +317,14 @@ class FuncODE(ODE):
     kind = _lib.SYS_FUNC
     MAX_D, MAX_ATOMS, MAX_DEGREE = 2048, 2048, 3
     FUNCTIONS = _lib.FUNC_FN
+    LABEL, DESTROY = 'FuncODE', 'nngp_func_destroy'
 
     def __init__(self, atoms, terms, u0, mn=None, mx=None, name='FuncODE', normalization=None, **kwargs):
-        u0 = np.array(u0, dtype=float)
-        if u0.ndim != 1 or not 1 <= u0.shape[0] <= self.MAX_D:
-            raise ValueError(f'FuncODE: u0 must be a vector of 1..{self.MAX_D} components')
-        d = u0.shape[0]
+        u0, d = self._state(u0)
         atoms = list(atoms)
         if len(atoms) > self.MAX_ATOMS:
             raise ValueError(f'FuncODE: {len(atoms)} atoms (at most {self.MAX_ATOMS})')
-        if len(terms) != d:
-            raise ValueError(f'FuncODE: {len(terms)} rows of terms for d = {d}')
-        if normalization is not None and normalization.lower() == '-11':
-            if mn is None or mx is None:
-                raise ValueError("FuncODE: normalization='-11' needs mn and mx")
-            mn = np.broadcast_to(np.asarray(mn, dtype=float), (d,)).copy()
-            mx = np.broadcast_to(np.asarray(mx, dtype=float), (d,)).copy()
+        mn, mx = self._bounds(terms, d, mn, mx, normalization)
         recs, canon = (_lib.CFuncAtom * max(len(atoms), 1))(), []
         for q, atom in enumerate(atoms):
             rec = self._atom(q, atom, d)
@@ -309,27 +333,13 @@ class FuncODE(ODE):
             c, j = second if second is not None else (0.0, -1)
             recs[q] = _lib.CFuncAtom(self.FUNCTIONS[fn], i, j, int(b is not None), a, c, 0.0 if b is None else b)
         nw = d + len(atoms)
-        row_ptr, coef, idx = [0], [], []
-        for c, row in enumerate(terms):
-            for coef_t, ind in row:
-                ind = [int(i) for i in ind]
-                if len(ind) > self.MAX_DEGREE:
-                    raise ValueError(f'FuncODE: row {c} has a term of degree {len(ind)} (at most {self.MAX_DEGREE})')
-                if any(not 0 <= i < nw for i in ind):
-                    raise ValueError(f'FuncODE: row {c} has an index outside [0, d + n_atoms = {nw})')
-                if not np.isfinite(coef_t):
-                    raise ValueError(f'FuncODE: row {c} has a coefficient that is not finite')
-                coef.append(float(coef_t))
-                idx.append(ind + [-1] * (self.MAX_DEGREE - len(ind)))
-            row_ptr.append(len(coef))
+        self._pack_terms(terms, nw, f'[0, d + n_atoms = {nw})')
         self.atoms = canon   # (fn, (a, i), (c, j) or None, b or None)
-        self.terms = [[(float(a), tuple(int(i) for i in ind)) for a, ind in row] for row in terms]
         self._atoms = recs
-        self._row_ptr = np.array(row_ptr, dtype=np.int32)
-        self._coef = np.array(coef, dtype=np.float64)
-        self._idx = np.array(idx, dtype=np.int16).reshape(-1, 3)
-        self._handle = None
         super().__init__(name, mn, mx, u0, normalization=normalization, **kwargs)
+
+    def _create(self, handle_ref):
+        return _lib.lib().nngp_func_create(self.d, len(self.atoms), self._atoms, *self._term_args(), handle_ref)
 
     @classmethod
     def _atom(cls, q, atom, d):
@@ -358,29 +368,3 @@ class FuncODE(ODE):
                 raise ValueError(bad + f'has a state index outside [0, {d}) (atoms read the state only)')
             pairs.append((a, i))
         return fn, pairs[0], pairs[1] if len(pairs) == 2 else None, b
-
-    @property
-    def nx(self):
-        """nngp_system.nx of this kind: the table's handle, created on first use"""
-        if self._handle is None:
-            h = ctypes.c_int32(0)
-            _lib.check(_lib.lib().nngp_func_create(
-                self.d, len(self.atoms), self._atoms, len(self._coef),
-                self._row_ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                self._coef.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                self._idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), ctypes.byref(h)))
-            self._handle = int(h.value)
-        return self._handle
-
-    def destroy(self):
-        """Free the library's table now (else when the object goes); descriptors made from it are
-        refused from then on."""
-        h, self._handle = getattr(self, '_handle', None), None
-        if h is not None and _lib._lib is not None:
-            _lib._lib.nngp_func_destroy(h)   # after nngp_shutdown the table is gone already: ignored
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:   # interpreter teardown
-            pass

@@ -277,6 +277,48 @@ def test_func_and_poly_handles_are_separate_registries():
         L.nngp_func_destroy(h)
 
 
+def test_equal_func_and_poly_handles_name_different_tables():
+    """A func table (d = 2) and a poly table (d = 3) under the same handle number: each kind resolves
+    its own table and is refused the other's d, and destroying one leaves the other.  (n_slices = 0:
+    nngp_rk_adaptive returns right after the table lookup, before any HIP call.)"""
+    from nngp_amd import _lib
+    L = _lib.lib()
+    rc, h = _create(L, **GOOD)
+    assert rc == 0 and h >= 1
+    rp = (ctypes.c_int32 * 4)(0, 0, 0, 0)   # d = 3, no terms: valid
+    made, same, func_live = [], None, True
+
+    def lookup(kind, d):
+        cs = _lib.CSystem(kind, d, h, 0, (ctypes.c_double * 4)(), None)
+        rc = L.nngp_rk_adaptive(ctypes.byref(cs), 45, 0, None, None, 4, 1e-3, 1e-6, 0.0, 100, None, None, None, None)
+        return rc, L.nngp_last_error().decode()
+
+    try:
+        for _ in range(4096):   # each registry hands out its lowest free slot: h comes within h creations
+            p = ctypes.c_int32(0)
+            assert L.nngp_poly_create(3, 0, rp, None, None, ctypes.byref(p)) == 0
+            made.append(p.value)
+            if p.value == h:
+                same = p.value
+                break
+        assert same == h, f'no poly table with handle {h} after {len(made)} creations'
+        assert lookup(_lib.SYS_POLY, 3)[0] == 0
+        assert lookup(_lib.SYS_FUNC, 2)[0] == 0
+        rc, msg = lookup(_lib.SYS_POLY, 2)
+        assert rc == -1 and 'poly' in msg and 'd=2' in msg, msg
+        rc, msg = lookup(_lib.SYS_FUNC, 3)
+        assert rc == -1 and 'func' in msg and 'd=3' in msg, msg
+        assert L.nngp_func_destroy(h) == 0
+        func_live = False
+        assert lookup(_lib.SYS_POLY, 3)[0] == 0
+        assert lookup(_lib.SYS_FUNC, 2)[0] == -1
+    finally:
+        for p in made:
+            L.nngp_poly_destroy(p)
+        if func_live:
+            L.nngp_func_destroy(h)
+
+
 @pytest.mark.parametrize('case', ['unknown', 'destroyed', 'zero', 'other_d'])
 def test_library_refuses_bad_descriptors_without_a_gpu(case):
     """NNGP_E_ARG from the host-side lookup, before any HIP call (the pointers are placeholders that
