@@ -124,6 +124,94 @@ struct HitMean {
 uint64_t *sel_prof_marks();
 void sel_prof_report(const char *what);
 
+// ---- the correction sweeps' argument bundles (plain aggregates; passed by const reference) ----
+struct Coarse {     // the coarse propagator G and its time grid: slice i runs t[i] -> t[i+1]
+    const nngp_system *sys; int tableau, step_mode; int64_t steps; const double *t;
+    int run(int i, const double *u, double *ug, hipStream_t st) const {   // ug = G(t[i], t[i+1], u)
+        return nngp_rk_batch(sys, tableau, step_mode, 1, t + i, t + i + 1, steps, u, ug, st);
+    }
+};
+struct TrainSet {   // the training set: X[rows][d] -> Y[rows][d]
+    const double *X, *Y; int64_t rows; int d;
+};
+struct FitSet {     // the Nelder-Mead fit settings of one prediction
+    int m, n_jitter; const double *jitter_exp_host; int n_restarts; double fatol, xatol; int maxfev;
+    int64_t n_fits(int d) const { return (int64_t)d * n_jitter * n_restarts; }
+};
+// The speculative references a prediction may be given (all null: no speculation): the ordered
+// neighbour list a speculative batch assumed for this query, that batch's fits and the device hit
+// flag; the same of the re-speculation window (hit 2); the host-mapped copy of the hit code; and the
+// completion counter (and error word) of a batch whose fits may still be running.
+struct SpecRefs {
+    const int32_t *spec_idx; const double *spec_fits; int32_t *hit_flag;
+    const int32_t *spec2_idx; const double *spec2_fits; int32_t *host_flag;
+    const int32_t *wait_done; int32_t *wait_err;
+};
+struct PredOut {    // a prediction's outputs: preds = mean, out = mean + bias (or null), every fit (or null)
+    double *preds; const double *bias; double *out, *fits_out;
+};
+
+// ---- workspace layouts: pure functions of sizes and a base pointer (no HIP call).  A null base is
+// the sizing pass: every pointer null, .bytes what workspace() is asked for.
+struct Carver {
+    char *base;
+    size_t off = 0;
+    template <class T> T *take(size_t n) {
+        T *p = base ? (T *)(base + off) : nullptr;
+        off += sizeof(T) * n;
+        return p;
+    }
+};
+// slot 0, one prediction: what the kNN, the select, the fits and the mean hand to each other (also the
+// fused chain's select and gdist): dist[rows] | D2[m*m] | kd2[m] | ymT[d*m] | idx[64] | fits[n_fits][4]
+struct PredWs {
+    double *dist, *D2, *kd2, *ymT; int32_t *idx; double *fits; size_t bytes;
+};
+inline PredWs pred_ws_carve(char *base, int64_t rows, int d, int m, int64_t n_fits) {
+    Carver c{base};   // (a braced list is evaluated in order)
+    PredWs w{c.take<double>((size_t)rows), c.take<double>((size_t)m * m), c.take<double>((size_t)m),
+             c.take<double>((size_t)d * m), c.take<int32_t>(64), c.take<double>(4 * (size_t)n_fits), 0};
+    w.bytes = c.off;
+    return w;
+}
+// slot 2, the speculative sweep (nq slices, window W, hst HitMean doubles per slice or 0):
+//   Qg[nq][d] | gtmp[d] | spec_fits[nq][n_fits][4] | W > 0: Qr[W][d] | gtmp2[d] | spec2_fits[nq][n_fits][4]
+//   | spec_idx[nq][m] | flags[nq] | done[nq] | W > 0: spec2_idx[nq][m]
+//   | hst > 0, 8-byte aligned: AP1[nq][hst] | AP2[nq][hst] | pre1[nq] | pre2[nq]
+struct SpecWs {
+    double *Qg, *gtmp, *spec_fits, *Qr, *gtmp2, *spec2_fits;
+    int32_t *spec_idx, *flags, *done, *spec2_idx;
+    double *AP1, *AP2; int32_t *pre1, *pre2; size_t bytes;
+};
+inline SpecWs spec_ws_carve(char *base, int64_t nq, int d, int m, int64_t n_fits, int W, size_t hst) {
+    Carver c{base};
+    SpecWs w{};
+    const size_t q = (size_t)nq, fits = q * (size_t)n_fits * 4;
+    w.Qg = c.take<double>(q * d);
+    w.gtmp = c.take<double>((size_t)d);
+    w.spec_fits = c.take<double>(fits);
+    if (W > 0) {
+        w.Qr = c.take<double>((size_t)W * d);
+        w.gtmp2 = c.take<double>((size_t)d);
+        w.spec2_fits = c.take<double>(fits);
+    }
+    w.spec_idx = c.take<int32_t>(q * m);
+    w.flags = c.take<int32_t>(q);
+    w.done = c.take<int32_t>(q);
+    if (W > 0) w.spec2_idx = c.take<int32_t>(q * m);
+    if (hst > 0) {
+        const size_t pad = ((c.off + 7) & ~(size_t)7) - c.off;
+        c.off += pad;
+        w.AP1 = c.take<double>(q * hst);
+        w.AP2 = c.take<double>(q * hst);
+        w.pre1 = c.take<int32_t>(q);
+        w.pre2 = c.take<int32_t>(q);
+        c.off += sizeof(double) - pad;   // a whole double is reserved for the alignment step
+    }
+    w.bytes = c.off;
+    return w;
+}
+
 // predict_impl's launches in parts (the speculative sweep issues the select, reads its hit flag on
 // the host, and then launches the fits only on a miss): all | kNN + select | fits + mean | mean only
 enum { PREDICT_ALL = 0, PREDICT_SELECT = 1, PREDICT_FITS_MEAN = 2, PREDICT_MEAN = 3, PREDICT_SELECT_ONLY = 4 };
@@ -131,24 +219,17 @@ enum { PREDICT_ALL = 0, PREDICT_SELECT = 1, PREDICT_FITS_MEAN = 2, PREDICT_MEAN 
 // then launches the select alone.  gdist_supported: systems with an in-kernel G (NNGP_GDIST=0: off)
 bool gdist_supported(const nngp_system *sys, int g_step_mode);
 bool g_side_supported(const nngp_system *sys, int g_step_mode);
-int gdist(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t g_steps, const double *t, int i,
-          const double *X, int64_t rows, int d, int m, int n_jitter, int n_restarts, const double *ui,
-          double *ug_next, hipStream_t st);
-int predict_impl(const double *X, const double *Y, int64_t rows, int d, const double *new_x, int m,
-                 int n_jitter, const double *jitter_exp_host, int n_restarts, const double *theta0,
-                 double fatol, double xatol, int maxfev, double *preds_out, const double *bias,
-                 double *out, double *fits_out, const int32_t *spec_idx, const double *spec_fits,
-                 int32_t *hit_flag, const int32_t *spec2_idx, const double *spec2_fits, int32_t *host_flag,
-                 hipStream_t st, int c0 = 0, int c1 = -1, const int32_t *wait_done = nullptr,
-                 int32_t *wait_err = nullptr, int phase = PREDICT_ALL, const HitMean *hm = nullptr,
-                 hipEvent_t bias_ready = nullptr);
+int gdist(const Coarse &G, int i, const TrainSet &T, const FitSet &F, const double *ui, double *ug_next,
+          hipStream_t st);
+// one prediction at new_x with its theta0 draws; coordinates [c0, c1) (c1 < 0: d)
+int predict_impl(const TrainSet &T, const FitSet &F, const double *new_x, const double *theta0, const PredOut &O,
+                 const SpecRefs &S, hipStream_t st, int c0 = 0, int c1 = -1, int phase = PREDICT_ALL,
+                 const HitMean *hm = nullptr, hipEvent_t bias_ready = nullptr);
 int gpfull_mean(const double *X, int64_t rows, int d, const double *q, const double *coef, const double *alpha,
                 const double *bias, double *out, hipStream_t st);
-int spec_batch(const double *X, const double *Y, int64_t rows, int d, const double *Q, int nq, int m,
-               int n_jitter, const double *jitter_exp_host, int n_restarts, const double *theta0,
-               double fatol, double xatol, int maxfev, int32_t *idx_out, double *fits_out, bool latency,
-               hipStream_t st, int slot = 1, int32_t *done = nullptr, hipEvent_t ev_select = nullptr,
-               double *pre_AP = nullptr, int32_t *pre_done = nullptr);
+int spec_batch(const TrainSet &T, const FitSet &F, const double *Q, int nq, const double *theta0, int32_t *idx_out,
+               double *fits_out, bool latency, hipStream_t st, int slot = 1, int32_t *done = nullptr,
+               hipEvent_t ev_select = nullptr, double *pre_AP = nullptr, int32_t *pre_done = nullptr);
 // gp_pre_kernel's workgroups per prediction (the HitMean target) for d coordinates at fit size m
 int pre_target(int d, int m);
 int pre_maxm(int m);   // the padded fit size of m
@@ -156,19 +237,39 @@ int pre_maxm(int m);   // the padded fit size of m
 void chain_release();   // nngp_shutdown's parts (nngp_gp.hip / nngp_sweep.hip / nngp_comm.hip)
 void sweep_release();
 void comm_release();
-// grow-only pool of timing events (nngp_sweep.hip): *out = n events
-int timing_events(size_t n, hipEvent_t **out);
+// The G time of a sweep (g_ms_out) without host synchronisation in the loop: event pairs around the
+// G launch of every stride-th slice, summed and scaled to all slices once the sweep has drained.
+// Each event record costs the host ~3 us on a chain whose hit slices are host-bound
+// (profiles/r05/sweep/), hence the stride (NNGP_G_TIME_EVERY, default 8; 1 = every slice).
+inline int g_time_stride() {
+    const int e = env_int("NNGP_G_TIME_EVERY", 8);
+    return e > 1 ? e : 1;
+}
+struct GTimer {
+    hipEvent_t *ev = nullptr; float *out = nullptr; int64_t slices = 0; int stride = 1;
+    // *g_ms_out = 0; no events for a null g_ms_out or an empty (or negative) slice count
+    int begin(float *g_ms_out, int64_t n_slices, int every);
+    bool timed(size_t j) const { return ev && j % (size_t)stride == 0; }
+    // G of slice i (the sweep's j-th): u -> ug on st, inside its event pair when the slice is timed
+    int launch(const Coarse &G, int i, size_t j, const double *u, double *ug, hipStream_t st) const {
+        if (!timed(j)) return G.run(i, u, ug, st);
+        NNGP_HIP_CHECK(hipEventRecord(ev[2 * j], st));
+        const int rc = G.run(i, u, ug, st);
+        if (rc) return rc;
+        NNGP_HIP_CHECK(hipEventRecord(ev[2 * j + 1], st));
+        return NNGP_OK;
+    }
+    void drop() { ev = nullptr; }   // the time comes from elsewhere (the fused chain's clock)
+    // waits for the last timed pair; *g_ms_out = the pairs' sum, scaled by slices / timed slices
+    int finish() const;
+};
 bool chain_supported(const nngp_system *sys, int g_step_mode, int m);
 bool guess_chain_supported(const nngp_system *sys, int g_step_mode);
-int guess_chain(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t g_steps, const double *t, int I,
-                int nq, const double *UF, const double *UG, double *Q, double *gtmp, hipStream_t st);
-int chain_sweep(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t g_steps, const double *t, int I,
-                int N, int i0, double *U1, double *UG1, const double *X, const double *Y, int64_t rows, int m,
-                int n_jitter, const double *jitter_exp_host, int n_restarts, int32_t *flags,
-                const int32_t *spec_idx, const double *spec_fits, const int32_t *spec2_idx,
-                const double *spec2_fits, double *preds, int *stop_out, float *g_ms_out, hipStream_t st);
-int chain_miss_fits(int64_t rows, int d, int m, int n_jitter, const double *jitter_exp_host, int n_restarts,
-                    const double *theta0, double fatol, double xatol, int maxfev, double *preds,
-                    const double *bias, double *out, hipStream_t st);
+int guess_chain(const Coarse &G, int I, int nq, const double *UF, const double *UG, double *Q, double *gtmp,
+                hipStream_t st);
+// S: the batch's references at slice I (hit_flag = the sweep's flags[nq]; no host flag, no wait)
+int chain_sweep(const Coarse &G, int I, int N, int i0, double *U1, double *UG1, const TrainSet &T, const FitSet &F,
+                const SpecRefs &S, double *preds, int *stop_out, float *g_ms_out, hipStream_t st);
+int chain_miss_fits(const TrainSet &T, const FitSet &F, const double *theta0, const PredOut &O, hipStream_t st);
 
 }  // namespace nngp

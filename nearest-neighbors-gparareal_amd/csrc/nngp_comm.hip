@@ -365,12 +365,10 @@ namespace nngp {
 // own gather block, no collective -- so the split, the partial last block and the block placement
 // are checked on one GPU against the unsharded sweep (tests/test_gpu_distributed.py).
 // gather_elems: the caller's gather length, checked against ranks * chunk before any launch.
-static int sweep_sharded(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t g_steps, const double *t,
-                         int I, int N, double *U1, double *UG1, const double *X, const double *Y, int64_t rows,
-                         int m, int n_jitter, const double *jitter_exp_host, int n_restarts, const double *theta0,
-                         double fatol, double xatol, int maxfev, double *gather, size_t gather_elems,
-                         int emulate_ranks, float *g_ms_out, void *stream) {
-    NNGP_REQUIRE(sys && t && U1 && UG1 && X && Y && theta0 && gather, "null argument");
+static int sweep_sharded(const Coarse &G, int I, int N, double *U1, double *UG1, const TrainSet &T, const FitSet &F,
+                         const double *theta0, double *gather, size_t gather_elems, int emulate_ranks,
+                         float *g_ms_out, hipStream_t st) {
+    NNGP_REQUIRE(G.sys && G.t && U1 && UG1 && T.X && T.Y && theta0 && gather, "null argument");
     NNGP_REQUIRE(0 <= I && I <= N, "need 0 <= I <= N (I=%d N=%d)", I, N);
     int nranks = 0, rank = -1;
     {
@@ -385,62 +383,39 @@ static int sweep_sharded(const nngp_system *sys, int g_tableau, int g_step_mode,
     NNGP_REQUIRE(nranks >= 1, "no communicator: call nngp_comm_init first");
     NNGP_REQUIRE(emulate_ranks == 0 || (nranks == 1 && emulate_ranks >= 1),
                  "rank emulation needs a one-rank communicator (have %d ranks)", nranks);
-    const int d = sys->d;
+    const int d = T.d;
     const int vranks = emulate_ranks > 0 ? emulate_ranks : nranks;
     const int chunk = (d + vranks - 1) / vranks;   // parareal.shard_bounds(0, d, vranks, rank)
     NNGP_REQUIRE(gather_elems >= (size_t)vranks * chunk, "gather holds %zu doubles, the split needs %d x %d",
                  gather_elems, vranks, chunk);
     const int r_lo = emulate_ranks > 0 ? 0 : rank, r_hi = emulate_ranks > 0 ? vranks : rank + 1;
-    const int64_t n_fits = (int64_t)d * n_jitter * n_restarts;
-    hipStream_t st = (hipStream_t)stream;
+    const int64_t n_fits = F.n_fits(d);
     int err = 0;
     // zeros[d] for the update's (a - b) + c form
     double *zeros = (double *)workspace(sizeof(double) * (size_t)d, &err, 9);
     if (err) return err;
     NNGP_HIP_CHECK(hipMemsetAsync(zeros, 0, sizeof(double) * (size_t)d, st));
-    hipEvent_t *ev = nullptr;   // G launch timing from the sweep's event pool (summed at the end)
-    if (g_ms_out) {
-        *g_ms_out = 0.f;
-        if (N > I) {
-            const int rc0 = timing_events(2 * (size_t)(N - I), &ev);
-            if (rc0) return rc0;
-        }
-    }
-    int rc = NNGP_OK;
+    GTimer gt;   // every slice's G launch timed: the plain sum
+    int rc = gt.begin(g_ms_out, (int64_t)N - I, 1);
     for (int i = I; i < N && rc == NNGP_OK; i++) {
         const size_t j = (size_t)(i - I);
         const double *ui = U1 + (size_t)i * d;
         double *ug_next = UG1 + (size_t)(i + 1) * d;
-        if (ev) NNGP_HIP_CHECK(hipEventRecord(ev[2 * j], st));
-        rc = nngp_rk_batch(sys, g_tableau, g_step_mode, 1, t + i, t + i + 1, g_steps, ui, ug_next, stream);
-        if (rc) break;
-        if (ev) NNGP_HIP_CHECK(hipEventRecord(ev[2 * j + 1], st));
+        rc = gt.launch(G, i, j, ui, ug_next, st);
         for (int r = r_lo; r < r_hi && rc == NNGP_OK; r++) {
             const int c0 = std::min(r * chunk, d), c1 = std::min((r + 1) * chunk, d);
             if (c1 > c0)
-                rc = predict_impl(X, Y, rows, d, ui, m, n_jitter, jitter_exp_host, n_restarts,
-                                  theta0 + j * n_fits * 2, fatol, xatol, maxfev, gather + (size_t)r * chunk, nullptr,
-                                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st, c0, c1,
-                                  nullptr, nullptr);
+                rc = predict_impl(T, F, ui, theta0 + j * n_fits * 2, {gather + (size_t)r * chunk, nullptr, nullptr, nullptr},
+                                  SpecRefs{}, st, c0, c1);
         }
         if (rc) break;
         if (nranks > 1) {   // in place: this rank's block sits at rank * chunk of the gather buffer
             rc = comm_allgather(gather + (size_t)rank * chunk, gather, (size_t)chunk, st);
             if (rc) break;
         }
-        rc = nngp_parareal_update(d, gather, zeros, ug_next, U1 + (size_t)(i + 1) * d, stream);
+        rc = nngp_parareal_update(d, gather, zeros, ug_next, U1 + (size_t)(i + 1) * d, st);
     }
-    if (ev && rc == NNGP_OK) {   // sum the G launches once the sweep has drained
-        NNGP_HIP_CHECK(hipEventSynchronize(ev[2 * (N - I) - 1]));
-        float total = 0.f;
-        for (int j = 0; j < N - I; j++) {
-            float ms = 0.f;
-            NNGP_HIP_CHECK(hipEventElapsedTime(&ms, ev[2 * j], ev[2 * j + 1]));
-            total += ms;
-        }
-        *g_ms_out = total;
-    }
-    return rc;
+    return rc == NNGP_OK ? gt.finish() : rc;   // once the sweep has drained
 }
 
 }  // namespace nngp
@@ -457,9 +432,9 @@ extern "C" int nngp_correction_sweep_sharded(const nngp_system *sys, int g_table
         nranks = nngp::g_comm ? nngp::g_comm_ranks : 0;
     }
     const size_t need = nranks >= 1 && sys ? (size_t)nranks * ((sys->d + nranks - 1) / nranks) : 0;
-    return nngp::sweep_sharded(sys, g_tableau, g_step_mode, g_steps, t, I, N, U1, UG1, X, Y, rows, m, n_jitter,
-                               jitter_exp_host, n_restarts, theta0, fatol, xatol, maxfev, gather, need, 0, g_ms_out,
-                               stream);
+    return nngp::sweep_sharded({sys, g_tableau, g_step_mode, g_steps, t}, I, N, U1, UG1, {X, Y, rows, sys ? sys->d : 0},
+                               {m, n_jitter, jitter_exp_host, n_restarts, fatol, xatol, maxfev}, theta0, gather, need, 0,
+                               g_ms_out, (hipStream_t)stream);
 }
 
 extern "C" int nngp_correction_sweep_sharded_emulated(const nngp_system *sys, int g_tableau, int g_step_mode,
@@ -473,7 +448,7 @@ extern "C" int nngp_correction_sweep_sharded_emulated(const nngp_system *sys, in
         nngp::set_error("emulate_ranks must be >= 1");
         return NNGP_E_ARG;
     }
-    return nngp::sweep_sharded(sys, g_tableau, g_step_mode, g_steps, t, I, N, U1, UG1, X, Y, rows, m, n_jitter,
-                               jitter_exp_host, n_restarts, theta0, fatol, xatol, maxfev, gather, gather_elems,
-                               emulate_ranks, g_ms_out, stream);
+    return nngp::sweep_sharded({sys, g_tableau, g_step_mode, g_steps, t}, I, N, U1, UG1, {X, Y, rows, sys ? sys->d : 0},
+                               {m, n_jitter, jitter_exp_host, n_restarts, fatol, xatol, maxfev}, theta0, gather,
+                               gather_elems, emulate_ranks, g_ms_out, (hipStream_t)stream);
 }

@@ -380,38 +380,19 @@ extern "C" int nngp_elm_sweep(const nngp_system *sys, int g_tableau, int g_step_
     int rc = elm_check(d, degree, res_size, bias_h, C);
     if (rc) return rc;
     if ((rc = elm_predict_check(X, Y, H, rows, m)) != NNGP_OK) return rc;
-    if (g_ms_out) *g_ms_out = 0.f;
+    GTimer gt;
+    if ((rc = gt.begin(g_ms_out, (int64_t)N - I, g_time_stride())) != NNGP_OK) return rc;
     if (N == I) return NNGP_OK;
-    hipStream_t st = (hipStream_t)stream;
+    const Coarse G{sys, g_tableau, g_step_mode, g_steps, t};
     ElmScratch s;
     if ((rc = elm_scratch(d, degree, res_size, &s)) != NNGP_OK) return rc;
-    // G time as in nngp_correction_sweep: event pairs around every g_every-th slice's G, scaled
-    const int g_every = std::max(1, env_int("NNGP_G_TIME_EVERY", 8));
-    hipEvent_t *ev = nullptr;
-    if (g_ms_out && (rc = timing_events(2 * (size_t)(N - I), &ev)) != NNGP_OK) return rc;
     for (int i = I; i < N; i++) {
-        const size_t j = (size_t)(i - I);
         const double *ui = U1 + (size_t)i * d;
         double *ug_next = UG1 + (size_t)(i + 1) * d;
-        const bool timed = ev && j % (size_t)g_every == 0;
-        if (timed) NNGP_HIP_CHECK(hipEventRecord(ev[2 * j], st));
-        rc = nngp_rk_batch(sys, g_tableau, g_step_mode, 1, t + i, t + i + 1, g_steps, ui, ug_next, stream);
-        if (rc) return rc;
-        if (timed) NNGP_HIP_CHECK(hipEventRecord(ev[2 * j + 1], st));
+        if ((rc = gt.launch(G, i, (size_t)(i - I), ui, ug_next, (hipStream_t)stream)) != NNGP_OK) return rc;
         rc = elm_predict_impl(X, Y, H, rows, d, ui, m, degree, res_size, bias_h, C, nullptr, ug_next,
                               U1 + (size_t)(i + 1) * d, s, stream);
         if (rc) return rc;
     }
-    if (ev) {
-        const int ns = (N - I - 1) / g_every + 1;
-        NNGP_HIP_CHECK(hipEventSynchronize(ev[2 * (size_t)(ns - 1) * g_every + 1]));
-        float total = 0.f;
-        for (int k = 0; k < ns; k++) {
-            float ms = 0.f;
-            NNGP_HIP_CHECK(hipEventElapsedTime(&ms, ev[2 * (size_t)k * g_every], ev[2 * (size_t)k * g_every + 1]));
-            total += ms;
-        }
-        *g_ms_out = total * (float)(N - I) / (float)ns;
-    }
-    return NNGP_OK;
+    return gt.finish();
 }

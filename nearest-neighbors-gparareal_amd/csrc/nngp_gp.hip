@@ -1566,42 +1566,70 @@ extern "C" int nngp_gp_mean(int m, int d, const double *xm, const double *ym, co
 
 namespace nngp {
 
+// the slot-0 prediction workspace of (T, F), carved (pred_ws_carve)
+static int pred_workspace(const TrainSet &T, const FitSet &F, PredWs *w) {
+    const int64_t n_fits = F.n_fits(T.d);
+    int err = 0;
+    char *ws = (char *)workspace(pred_ws_carve(nullptr, T.rows, T.d, F.m, n_fits).bytes, &err);
+    if (err) return err;
+    *w = pred_ws_carve(ws, T.rows, T.d, F.m, n_fits);
+    return NNGP_OK;
+}
+
+// the fits + mean arguments of dc coordinates from the select's workspace (a: jitters filled)
+static void fit_args(NMArgs &a, const PredWs &w, const FitSet &F, int dc, const double *theta0, const PredOut &O) {
+    a.m = F.m; a.d = dc; a.n_fits = (int)F.n_fits(dc);
+    a.D2 = w.D2; a.kd2 = w.kd2; a.Y = w.ymT; a.ys_c = F.m; a.ys_r = 1;
+    a.theta0 = theta0; a.fatol = F.fatol; a.xatol = F.xatol; a.maxfev = F.maxfev;
+    a.R = F.n_restarts;
+    a.fits_out = w.fits;
+    a.preds = O.preds; a.bias = O.bias; a.out = O.out;
+}
+
+// A prediction's launches after its select: the fits (a wave each, or the packed fits with the tail
+// hand-off -- a coordinate's fits exceed one workgroup, or speculation), then the per-coordinate
+// arg-min + posterior mean (+ bias) kernel.  bias_ready: the bias (UG1[i+1] = G(U1[i])) comes from
+// another stream; the mean waits for it.
+static int fits_then_mean(NMArgs &a, hipStream_t st, hipEvent_t bias_ready = nullptr) {
+    int rc;
+    if (use_spec(a.n_fits, a.m)) {
+        rc = run_nm_spec(a, st);
+    } else {
+        NMArgs u = a;
+        u.preds = nullptr; u.out = nullptr; u.bias = nullptr;
+        rc = run_nm_parked(u, st);
+    }
+    if (rc) return rc;
+    if (bias_ready) NNGP_HIP_CHECK(hipStreamWaitEvent(st, bias_ready, 0));
+    return run_mean(a, st);
+}
+
 // One prediction (NNGP_p.predict).  With spec_idx (the ordered neighbour list a speculative batch
 // assumed for this query), spec_fits (that batch's fits for it) and hit_flag (device int):
 // knn_select sets *hit_flag = (actual list == spec_idx); the fits launch then exits at once on a
 // hit and the arg-min/mean kernel reads spec_fits -- bitwise what it would have computed, since a
 // fit depends only on (the ordered neighbours, its coordinate, jitter and theta0).
-int predict_impl(const double *X, const double *Y, int64_t rows, int d, const double *new_x, int m,
-                 int n_jitter, const double *jitter_exp_host, int n_restarts, const double *theta0,
-                 double fatol, double xatol, int maxfev, double *preds_out, const double *bias,
-                 double *out, double *fits_out, const int32_t *spec_idx, const double *spec_fits,
-                 int32_t *hit_flag, const int32_t *spec2_idx, const double *spec2_fits, int32_t *host_flag,
-                 hipStream_t st, int c0, int c1, const int32_t *wait_done, int32_t *wait_err, int phase,
-                 const HitMean *hm, hipEvent_t bias_ready) {
-    NNGP_REQUIRE(X && Y && new_x && theta0 && preds_out, "null array argument");
+int predict_impl(const TrainSet &T, const FitSet &F, const double *new_x, const double *theta0, const PredOut &O,
+                 const SpecRefs &S, hipStream_t st, int c0, int c1, int phase, const HitMean *hm,
+                 hipEvent_t bias_ready) {
+    const double *X = T.X, *Y = T.Y;
+    const int64_t rows = T.rows;
+    const int d = T.d, m = F.m;
+    NNGP_REQUIRE(X && Y && new_x && theta0 && O.preds, "null array argument");
     NNGP_REQUIRE(phase >= PREDICT_ALL && phase <= PREDICT_SELECT_ONLY, "bad predict phase %d", phase);
     if (c1 < 0) c1 = d;
     NNGP_REQUIRE(0 <= c0 && c0 < c1 && c1 <= d, "bad coordinate range [%d, %d) of d=%d", c0, c1, d);
     NNGP_REQUIRE(m >= 1 && m <= MAX_M, "need 1 <= m <= %d (got %d)", MAX_M, m);
     NNGP_REQUIRE(m <= rows, "m=%d exceeds training rows=%lld", m, (long long)rows);
-    NNGP_REQUIRE(d >= 1 && n_restarts >= 1 && maxfev >= 1, "bad d / n_restarts / maxfev");
-    const bool spec = spec_idx && spec_fits && hit_flag;
+    NNGP_REQUIRE(d >= 1 && F.n_restarts >= 1 && F.maxfev >= 1, "bad d / n_restarts / maxfev");
+    const bool spec = S.spec_idx && S.spec_fits && S.hit_flag;
     NMArgs a{};
-    int rc = fill_jitters(a, n_jitter, jitter_exp_host);
+    int rc = fill_jitters(a, F.n_jitter, F.jitter_exp_host);
     if (rc) return rc;
-    // workspace: dist[rows] | D2[m*m] | kd2[m] | ymT[d*m] | idx[m] (int32) | fits[n_fits][4]
-    // (the fits scratch serves the unfused paths when the caller passes no fits_out)
-    const size_t nd = (size_t)rows + (size_t)m * m + m + (size_t)d * m;
-    const size_t n_fits = (size_t)d * n_jitter * n_restarts;
-    int err = 0;
-    char *ws = (char *)workspace(sizeof(double) * nd + sizeof(int32_t) * 64 + sizeof(double) * 4 * n_fits, &err);
-    if (err) return err;
-    double *dist = (double *)ws;
-    double *D2 = dist + rows;
-    double *kd2 = D2 + (size_t)m * m;
-    double *ymT = kd2 + m;
-    int32_t *idx = (int32_t *)(ymT + (size_t)d * m);
-    double *fits_ws = (double *)(ws + sizeof(double) * nd + sizeof(int32_t) * 64);
+    PredWs w;   // (its fits scratch serves the unfused paths when the caller passes no fits_out)
+    if ((rc = pred_workspace(T, F, &w)) != NNGP_OK) return rc;
+    double *dist = w.dist, *D2 = w.D2, *kd2 = w.kd2, *ymT = w.ymT;
+    int32_t *idx = w.idx;
     if (phase == PREDICT_ALL || phase == PREDICT_SELECT || phase == PREDICT_SELECT_ONLY) {
         if (phase != PREDICT_SELECT_ONLY) {   // (SELECT_ONLY: gdist wrote the distances)
             hipLaunchKernelGGL(knn_dist_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, X, rows,
@@ -1612,11 +1640,11 @@ int predict_impl(const double *X, const double *Y, int64_t rows, int d, const do
         const bool sel_d2 = !wave_d2 && !pair_d2;
         launch_knn_select(dim3(1), knn_xs_bytes(m, d), st, dist, rows, m, X, Y, d, new_x, idx, (double *)nullptr,
                           ymT, sel_d2 ? D2 : (double *)nullptr, sel_d2 ? kd2 : (double *)nullptr,
-                          spec ? spec_idx : (const int32_t *)nullptr,
-                          spec ? hit_flag : (int32_t *)nullptr, knn_xs_doubles(m, d),
-                          spec ? spec2_idx : (const int32_t *)nullptr, spec ? host_flag : (int32_t *)nullptr,
+                          spec ? S.spec_idx : (const int32_t *)nullptr,
+                          spec ? S.hit_flag : (int32_t *)nullptr, knn_xs_doubles(m, d),
+                          spec ? S.spec2_idx : (const int32_t *)nullptr, spec ? S.host_flag : (int32_t *)nullptr,
                           [&] {
-                              HitMean h = (spec && host_flag && hm && sel_d2 && kd2) ? *hm : HitMean{};
+                              HitMean h = (spec && S.host_flag && hm && sel_d2 && kd2) ? *hm : HitMean{};
                               h.marks = sel_prof_marks();
                               return h;
                           }());
@@ -1635,53 +1663,35 @@ int predict_impl(const double *X, const double *Y, int64_t rows, int d, const do
     // coordinates [c0, c1) only (the multi-rank sweep's share): the fits and means of those
     // columns, in the same product(coord, jitter, restart) order with their own theta0 draws
     const int dc = c1 - c0;
-    const size_t nfc = (size_t)n_jitter * n_restarts;
-    a.m = m; a.d = dc; a.n_fits = (int)(dc * nfc);
-    a.D2 = D2; a.kd2 = kd2; a.Y = ymT + (size_t)c0 * m; a.ys_c = m; a.ys_r = 1;
-    a.theta0 = theta0 + (size_t)c0 * nfc * 2; a.fatol = fatol; a.xatol = xatol; a.maxfev = maxfev;
-    a.R = n_restarts;
-    a.fits_out = fits_out ? fits_out : fits_ws;
-    a.preds = preds_out; a.bias = bias; a.out = out;
+    const size_t nfc = (size_t)F.n_fits(1);
+    fit_args(a, w, F, dc, theta0 + (size_t)c0 * nfc * 2, O);
+    a.Y = ymT + (size_t)c0 * m;
+    if (O.fits_out) a.fits_out = O.fits_out;
     if (spec) {
-        a.skip = hit_flag;
-        a.fits_alt = spec_fits;
-        a.fits_alt2 = spec2_fits;
-        if (wait_done) {   // the batch's fits may still be running (overlapped sweep)
-            a.wait_done = wait_done;
-            a.wait_n = (int)n_fits;
-            a.err = wait_err;
+        a.skip = S.hit_flag;
+        a.fits_alt = S.spec_fits;
+        a.fits_alt2 = S.spec2_fits;
+        if (S.wait_done) {   // the batch's fits may still be running (overlapped sweep)
+            a.wait_done = S.wait_done;
+            a.wait_n = (int)F.n_fits(d);
+            a.err = S.wait_err;
             const double us = std::max(0, env_int("NNGP_SPEC_WAIT_US", 2000000));
             a.wait_ticks = (uint64_t)(us * device_wallclock_khz() / 1e3);
         }
     }
-    // bias_ready: the bias (UG1[i+1] = G(U1[i])) comes from another stream; the mean waits for it
-    auto mean = [&](NMArgs &ma) -> int {
-        if (bias_ready) NNGP_HIP_CHECK(hipStreamWaitEvent(st, bias_ready, 0));
-        return run_mean(ma, st);
-    };
     if (phase == PREDICT_MEAN) {   // the select's hit is known: the fits are the speculative batch's
         NNGP_REQUIRE(spec, "predict: the mean-only phase needs the speculative fits");
-        return mean(a);
+        if (bias_ready) NNGP_HIP_CHECK(hipStreamWaitEvent(st, bias_ready, 0));
+        return run_mean(a, st);
     }
-    if (use_spec(a.n_fits, a.m)) {   // fits (a wave each), then arg-min + mean (+ bias) per coordinate
-        rc = run_nm_spec(a, st);
-        if (rc) return rc;
-        return mean(a);
-    }
-    if (!spec && nm_park_cap() == 0) {
+    if (!spec && nm_park_cap() == 0 && !use_spec(a.n_fits, a.m)) {   // fits + mean fused, a coordinate per group
         NMArgs fu = a;
-        fu.fits_out = fits_out;
+        fu.fits_out = O.fits_out;
         if (bias_ready) NNGP_HIP_CHECK(hipStreamWaitEvent(st, bias_ready, 0));   // (the mean is in the fits)
         rc = run_nm(fu, true, st);
         if (rc != NNGP_E_UNSUPPORTED) return rc;
     }
-    // the packed fits with the tail hand-off (or: a coordinate's fits exceed one workgroup, or
-    // speculation), then the per-coordinate arg-min + posterior mean kernel
-    NMArgs u = a;
-    u.preds = nullptr; u.out = nullptr; u.bias = nullptr;
-    rc = run_nm_parked(u, st);
-    if (rc) return rc;
-    return mean(a);
+    return fits_then_mean(a, st, bias_ready);
 }
 
 // gp_pre_kernel over nq predictions of a batch (p: the batch's fits arguments with its per-prediction
@@ -1703,15 +1713,17 @@ static int run_pre(const NMArgs &p, double *AP, int32_t *pre_done, int nq, hipSt
 // prediction's own theta0 draws (theta0[nq][n_fits][2]).  One kNN-distance launch, one
 // kNN-select launch (a workgroup per query) and ONE packed fits launch (4 fits per wave over
 // all nq*n_fits fits) -- the throughput-shaped work that the sequential sweep then only looks up.
-int spec_batch(const double *X, const double *Y, int64_t rows, int d, const double *Q, int nq, int m,
-               int n_jitter, const double *jitter_exp_host, int n_restarts, const double *theta0,
-               double fatol, double xatol, int maxfev, int32_t *idx_out, double *fits_out, bool latency,
-               hipStream_t st, int slot, int32_t *done, hipEvent_t ev_select, double *pre_AP, int32_t *pre_done) {
+int spec_batch(const TrainSet &T, const FitSet &F, const double *Q, int nq, const double *theta0, int32_t *idx_out,
+               double *fits_out, bool latency, hipStream_t st, int slot, int32_t *done, hipEvent_t ev_select,
+               double *pre_AP, int32_t *pre_done) {
+    const double *X = T.X, *Y = T.Y;
+    const int64_t rows = T.rows;
+    const int d = T.d, m = F.m;
     NNGP_REQUIRE(nq >= 1 && m >= 1 && m <= MAX_M && m <= rows, "bad speculative batch shape");
     NMArgs a{};
-    int rc = fill_jitters(a, n_jitter, jitter_exp_host);
+    int rc = fill_jitters(a, F.n_jitter, F.jitter_exp_host);
     if (rc) return rc;
-    const size_t nfp = (size_t)d * n_jitter * n_restarts;
+    const size_t nfp = (size_t)F.n_fits(d);
     // slot-1 workspace: dist[nq][rows] | D2[nq][m*m] | ymT[nq][d*m]
     int err = 0;
     double *dist = (double *)workspace(sizeof(double) * (size_t)nq * ((size_t)rows + (size_t)m * m + (size_t)d * m),
@@ -1744,7 +1756,7 @@ int spec_batch(const double *X, const double *Y, int64_t rows, int d, const doub
     if (ev_select) NNGP_HIP_CHECK(hipEventRecord(ev_select, st));   // the lists are ready
     a.m = m; a.d = d; a.n_fits = (int)nfp;
     a.D2 = D2; a.Y = ymT; a.ys_c = m; a.ys_r = 1;
-    a.theta0 = theta0; a.fatol = fatol; a.xatol = xatol; a.maxfev = maxfev; a.R = n_restarts;
+    a.theta0 = theta0; a.fatol = F.fatol; a.xatol = F.xatol; a.maxfev = F.maxfev; a.R = F.n_restarts;
     a.fits_out = fits_out;
     a.qs_D2 = (int64_t)m * m; a.qs_Y = (int64_t)d * m; a.qs_th = (int64_t)nfp * 2; a.qs_fits = (int64_t)nfp * 4;
     a.jmajor = env_int("NNGP_NM_JMAJOR", 1);   // (run_nm_parked; Burgers 0.328 -> 0.317 s)
@@ -1812,7 +1824,10 @@ struct GArgs {
     int64_t g_steps;
 };
 
-static int g_args(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t g_steps, GArgs &g) {
+static int g_args(const Coarse &G, GArgs &g) {
+    const nngp_system *sys = G.sys;
+    const int g_tableau = G.tableau, g_step_mode = G.step_mode;
+    const int64_t g_steps = G.steps;
     g = GArgs{};
     const int d = sys->d, kind = sys->kind;
     if (kind == NNGP_SYS_BURGERS) {
@@ -1892,14 +1907,14 @@ bool guess_chain_supported(const nngp_system *sys, int g_step_mode) {
     return env_int("NNGP_GUESS_FUSED", 1) != 0 && g_in_kernel(sys, g_step_mode);
 }
 
-int guess_chain(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t g_steps, const double *t, int I,
-                int nq, const double *UF, const double *UG, double *Q, double *gtmp, hipStream_t st) {
-    NNGP_REQUIRE(g_in_kernel(sys, g_step_mode), "guess chain: no in-kernel G for this system");
+int guess_chain(const Coarse &G, int I, int nq, const double *UF, const double *UG, double *Q, double *gtmp,
+                hipStream_t st) {
+    NNGP_REQUIRE(g_in_kernel(G.sys, G.step_mode), "guess chain: no in-kernel G for this system");
     if (nq < 2) return NNGP_OK;
     GArgs g;
-    const int rc = g_args(sys, g_tableau, g_step_mode, g_steps, g);
+    const int rc = g_args(G, g);
     if (rc) return rc;
-    hipLaunchKernelGGL(guess_chain_kernel, dim3(1), dim3(64), 0, st, g, t, I, nq, sys->d, UF, UG, Q, gtmp);
+    hipLaunchKernelGGL(guess_chain_kernel, dim3(1), dim3(64), 0, st, g, G.t, I, nq, G.sys->d, UF, UG, Q, gtmp);
     NNGP_LAUNCH_CHECK();
     return NNGP_OK;
 }
@@ -1934,19 +1949,15 @@ bool g_side_supported(const nngp_system *sys, int g_step_mode) {
 
 // G of slice i and its query's distances into predict_impl's workspace (the same slot-0 layout and
 // size, so the select of PREDICT_SELECT_ONLY that follows finds them)
-int gdist(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t g_steps, const double *t, int i,
-          const double *X, int64_t rows, int d, int m, int n_jitter, int n_restarts, const double *ui,
-          double *ug_next, hipStream_t st) {
+int gdist(const Coarse &G, int i, const TrainSet &T, const FitSet &F, const double *ui, double *ug_next,
+          hipStream_t st) {
     GArgs g;
-    const int rc = g_args(sys, g_tableau, g_step_mode, g_steps, g);
+    int rc = g_args(G, g);
     if (rc) return rc;
-    const size_t nd = (size_t)rows + (size_t)m * m + m + (size_t)d * m;
-    const size_t n_fits = (size_t)d * n_jitter * n_restarts;
-    int err = 0;
-    double *dist = (double *)workspace(sizeof(double) * nd + sizeof(int32_t) * 64 + sizeof(double) * 4 * n_fits, &err);
-    if (err) return err;
-    hipLaunchKernelGGL(gdist_kernel, dim3((unsigned)((rows + 63) / 64 + 1)), dim3(64), 0, st, g, t[i], t[i + 1], X,
-                       rows, d, ui, dist, ug_next);
+    PredWs w;
+    if ((rc = pred_workspace(T, F, &w)) != NNGP_OK) return rc;
+    hipLaunchKernelGGL(gdist_kernel, dim3((unsigned)((T.rows + 63) / 64 + 1)), dim3(64), 0, st, g, G.t[i], G.t[i + 1],
+                       T.X, T.rows, T.d, ui, w.dist, ug_next);
     NNGP_LAUNCH_CHECK();
     return NNGP_OK;
 }
@@ -1985,43 +1996,35 @@ static int chain_launch(ChainArgs &c, int nb, size_t lds, hipStream_t st) {
 // Run the chain from slice i0 on stream st until the first miss (or N).  *stop_out = that slice:
 // its G output (UG1[stop+1]) and its select workspace (chain_miss_fits) are in place.  The call
 // returns after the kernel has drained; *g_ms_out += the in-kernel G time.
-int chain_sweep(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t g_steps, const double *t, int I,
-                int N, int i0, double *U1, double *UG1, const double *X, const double *Y, int64_t rows, int m,
-                int n_jitter, const double *jitter_exp_host, int n_restarts, int32_t *flags,
-                const int32_t *spec_idx, const double *spec_fits, const int32_t *spec2_idx,
-                const double *spec2_fits, double *preds, int *stop_out, float *g_ms_out, hipStream_t st) {
-    const int d = sys->d;
-    NNGP_REQUIRE(chain_supported(sys, g_step_mode, m) && I <= i0 && i0 < N && m <= rows, "chain: unsupported shape");
+int chain_sweep(const Coarse &G, int I, int N, int i0, double *U1, double *UG1, const TrainSet &T, const FitSet &F,
+                const SpecRefs &S, double *preds, int *stop_out, float *g_ms_out, hipStream_t st) {
+    const int d = T.d, m = F.m;
+    const int64_t rows = T.rows, n_fits = F.n_fits(d);
+    NNGP_REQUIRE(chain_supported(G.sys, G.step_mode, m) && I <= i0 && i0 < N && m <= rows, "chain: unsupported shape");
     ChainRes *res = nullptr;
     int rc = chain_resources(&res);
     if (rc) return rc;
     ChainArgs c{};
-    rc = fill_jitters(c.a, n_jitter, jitter_exp_host);
+    rc = fill_jitters(c.a, F.n_jitter, F.jitter_exp_host);
     if (rc) return rc;
-    // slot-0 workspace, predict_impl's layout: dist[rows] | D2[m*m] | kd2[m] | ymT[d*m] | idx[64] | fits
-    const size_t nd = (size_t)rows + (size_t)m * m + m + (size_t)d * m;
-    const size_t n_fits = (size_t)d * n_jitter * n_restarts;
-    int err = 0;
-    char *ws = (char *)workspace(sizeof(double) * nd + sizeof(int32_t) * 64 + sizeof(double) * 4 * n_fits, &err);
-    if (err) return err;
-    double *dist = (double *)ws;
-    double *D2 = dist + rows, *kd2 = D2 + (size_t)m * m, *ymT = kd2 + m;
-    c.a.m = m; c.a.d = d; c.a.n_fits = (int)n_fits; c.a.D2 = D2; c.a.kd2 = kd2; c.a.Y = ymT;
-    c.a.ys_c = m; c.a.ys_r = 1; c.a.R = n_restarts;
+    PredWs w;
+    if ((rc = pred_workspace(T, F, &w)) != NNGP_OK) return rc;
+    c.a.m = m; c.a.d = d; c.a.n_fits = (int)n_fits; c.a.D2 = w.D2; c.a.kd2 = w.kd2; c.a.Y = w.ymT;
+    c.a.ys_c = m; c.a.ys_r = 1; c.a.R = F.n_restarts;
     GArgs ga;
-    rc = g_args(sys, g_tableau, g_step_mode, g_steps, ga);
+    rc = g_args(G, ga);
     if (rc) return rc;
     c.la = ga.la; c.fa = ga.fa; c.gkind = ga.gkind; c.ept = ga.ept;
     c.sys = ga.sys; c.order = ga.order; c.lin = ga.lin; c.norm = ga.norm; c.g_steps = ga.g_steps;
-    c.t = t; c.I = I; c.N = N; c.i0 = i0;
-    c.U1 = U1; c.UG1 = UG1; c.X = X; c.Yd = Y; c.rows = rows;
+    c.t = G.t; c.I = I; c.N = N; c.i0 = i0;
+    c.U1 = U1; c.UG1 = UG1; c.X = T.X; c.Yd = T.Y; c.rows = rows;
     const int64_t per = (rows + 255) / 256;
     c.kk = per <= 2 ? 2 : (per <= 4 ? 4 : (per <= 8 ? 8 : (per <= 16 ? 16 : 0)));
     c.xs_doubles = knn_xs_doubles(m, d);
     c.n_mean_blk = (d + 15) / 16;
-    c.dist = dist; c.idx = (int32_t *)(ymT + (size_t)d * m);
-    c.flags = flags; c.spec_idx = spec_idx; c.spec2_idx = spec2_idx;
-    c.spec_fits = spec_fits; c.spec2_fits = spec2_fits; c.n_fits = (int64_t)n_fits;
+    c.dist = w.dist; c.idx = w.idx;
+    c.flags = S.hit_flag; c.spec_idx = S.spec_idx; c.spec2_idx = S.spec2_idx;
+    c.spec_fits = S.spec_fits; c.spec2_fits = S.spec2_fits; c.n_fits = n_fits;
     c.preds = preds;
     c.bar = res->bar;
     c.stop = res->stop;
@@ -2032,7 +2035,7 @@ int chain_sweep(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t 
     // the grid-barrier timeout: other workgroups wait at barrier 1 while block 0 integrates G, so
     // it scales with the coarse step count (4 us per step covers every G kernel here, RK8 Burgers
     // ~1.4 us) and is never below NNGP_CHAIN_BARRIER_US (default 2 s)
-    const double bar_us = std::max((double)std::max(0, env_int("NNGP_CHAIN_BARRIER_US", 2000000)), 4.0 * (double)g_steps);
+    const double bar_us = std::max((double)std::max(0, env_int("NNGP_CHAIN_BARRIER_US", 2000000)), 4.0 * (double)G.steps);
     c.bar_ticks = (uint64_t)(bar_us * res->tick_khz / 1e3);
     const int maxm = maxm_for(m);
     const size_t lds = std::max(knn_xs_bytes(m, d),
@@ -2085,35 +2088,14 @@ int chain_sweep(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t 
 // The fits of the slice the chain stopped at (a miss), from the chain's select workspace, then
 // the arg-min, mean and U1[stop+1] = mean + UG1[stop+1]: predict_impl's launches after its select
 // on a speculation miss, so the result is bitwise the unfused sweep's.
-int chain_miss_fits(int64_t rows, int d, int m, int n_jitter, const double *jitter_exp_host, int n_restarts,
-                    const double *theta0, double fatol, double xatol, int maxfev, double *preds,
-                    const double *bias, double *out, hipStream_t st) {
+int chain_miss_fits(const TrainSet &T, const FitSet &F, const double *theta0, const PredOut &O, hipStream_t st) {
     NMArgs a{};
-    int rc = fill_jitters(a, n_jitter, jitter_exp_host);
+    int rc = fill_jitters(a, F.n_jitter, F.jitter_exp_host);
     if (rc) return rc;
-    const size_t nd = (size_t)rows + (size_t)m * m + m + (size_t)d * m;
-    const size_t n_fits = (size_t)d * n_jitter * n_restarts;
-    int err = 0;
-    char *ws = (char *)workspace(sizeof(double) * nd + sizeof(int32_t) * 64 + sizeof(double) * 4 * n_fits, &err);
-    if (err) return err;
-    double *D2 = (double *)ws + rows, *kd2 = D2 + (size_t)m * m, *ymT = kd2 + m;
-    double *fits_ws = (double *)(ws + sizeof(double) * nd + sizeof(int32_t) * 64);
-    a.m = m; a.d = d; a.n_fits = (int)n_fits;
-    a.D2 = D2; a.kd2 = kd2; a.Y = ymT; a.ys_c = m; a.ys_r = 1;
-    a.theta0 = theta0; a.fatol = fatol; a.xatol = xatol; a.maxfev = maxfev;
-    a.R = n_restarts;
-    a.fits_out = fits_ws;
-    a.preds = preds; a.bias = bias; a.out = out;
-    if (use_spec(a.n_fits, a.m)) {
-        rc = run_nm_spec(a, st);
-        if (rc) return rc;
-        return run_mean(a, st);
-    }
-    NMArgs u = a;
-    u.preds = nullptr; u.out = nullptr; u.bias = nullptr;
-    rc = run_nm_parked(u, st);
-    if (rc) return rc;
-    return run_mean(a, st);
+    PredWs w;
+    if ((rc = pred_workspace(T, F, &w)) != NNGP_OK) return rc;
+    fit_args(a, w, F, T.d, theta0, O);
+    return fits_then_mean(a, st);
 }
 
 }  // namespace nngp
@@ -2129,16 +2111,14 @@ extern "C" int nngp_predict(const double *X, const double *Y, int64_t rows, int 
                             const double *theta0, double fatol, double xatol, int maxfev,
                             double *preds_out, const double *bias, double *out, double *fits_out,
                             void *stream) {
-    return nngp::predict_impl(X, Y, rows, d, new_x, m, n_jitter, jitter_exp_host, n_restarts, theta0, fatol,
-                              xatol, maxfev, preds_out, bias, out, fits_out, nullptr, nullptr, nullptr, nullptr,
-                              nullptr, nullptr, (hipStream_t)stream, 0, d, nullptr, nullptr);
+    return nngp::predict_impl({X, Y, rows, d}, {m, n_jitter, jitter_exp_host, n_restarts, fatol, xatol, maxfev}, new_x,
+                              theta0, {preds_out, bias, out, fits_out}, SpecRefs{}, (hipStream_t)stream, 0, d);
 }
 
 extern "C" int nngp_predict_range(const double *X, const double *Y, int64_t rows, int d, const double *new_x,
                                   int m, int n_jitter, const double *jitter_exp_host, int n_restarts,
                                   const double *theta0, int c0, int c1, double fatol, double xatol, int maxfev,
                                   double *preds_out, void *stream) {
-    return nngp::predict_impl(X, Y, rows, d, new_x, m, n_jitter, jitter_exp_host, n_restarts, theta0, fatol,
-                              xatol, maxfev, preds_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                              nullptr, nullptr, nullptr, (hipStream_t)stream, c0, c1, nullptr, nullptr);
+    return nngp::predict_impl({X, Y, rows, d}, {m, n_jitter, jitter_exp_host, n_restarts, fatol, xatol, maxfev}, new_x,
+                              theta0, {preds_out, nullptr, nullptr, nullptr}, SpecRefs{}, (hipStream_t)stream, c0, c1);
 }

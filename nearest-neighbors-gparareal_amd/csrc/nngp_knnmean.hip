@@ -204,8 +204,10 @@ extern "C" int nngp_knn_mean_sweep(const nngp_system *sys, int g_tableau, int g_
     if (rc) return rc;
     if ((rc = knnmean_check_m(m, rows)) != NNGP_OK) return rc;
     NNGP_REQUIRE(I >= 0, "I must be >= 0 (got %d)", I);
-    if (g_ms_out) *g_ms_out = 0.f;
+    GTimer gt;   // (N < I: an empty sweep)
+    if ((rc = gt.begin(g_ms_out, (int64_t)N - I, g_time_stride())) != NNGP_OK) return rc;
     if (N <= I) return NNGP_OK;
+    const Coarse G{sys, g_tableau, g_step_mode, g_steps, t};
     hipStream_t st = (hipStream_t)stream;
     KnnMeanArgs a;
     a.X = X; a.Y = Y; a.rows = rows; a.d = d; a.n_q = 1;
@@ -220,19 +222,11 @@ extern "C" int nngp_knn_mean_sweep(const nngp_system *sys, int g_tableau, int g_
     a.idx = (int32_t *)(ws + dist_bytes);
     a.counter = (unsigned *)(a.idx + KNNMEAN_MAX_M);
     NNGP_HIP_CHECK(hipMemsetAsync(a.counter, 0, sizeof(unsigned), st));   // once per sweep: every launch leaves 0
-    // G time as in nngp_elm_sweep: event pairs around every g_every-th slice's G, scaled
-    const int g_every = std::max(1, env_int("NNGP_G_TIME_EVERY", 8));
-    hipEvent_t *ev = nullptr;
-    if (g_ms_out && (rc = timing_events(2 * (size_t)(N - I), &ev)) != NNGP_OK) return rc;
     for (int i = I; i < N; i++) {
         const size_t j = (size_t)(i - I);
         const double *ui = U1 + (size_t)i * d;
         double *ug_next = UG1 + (size_t)(i + 1) * d;
-        const bool timed = ev && j % (size_t)g_every == 0;
-        if (timed) NNGP_HIP_CHECK(hipEventRecord(ev[2 * j], st));
-        rc = nngp_rk_batch(sys, g_tableau, g_step_mode, 1, t + i, t + i + 1, g_steps, ui, ug_next, stream);
-        if (rc) return rc;
-        if (timed) NNGP_HIP_CHECK(hipEventRecord(ev[2 * j + 1], st));
+        if ((rc = gt.launch(G, i, j, ui, ug_next, st)) != NNGP_OK) return rc;
         a.Q = ui;
         a.out = preds ? preds + j * (size_t)d : nullptr;
         a.bias = ug_next;
@@ -240,16 +234,5 @@ extern "C" int nngp_knn_mean_sweep(const nngp_system *sys, int g_tableau, int g_
         knnmean_launch<true>(a, st);
         NNGP_LAUNCH_CHECK();
     }
-    if (ev) {
-        const int ns = (N - I - 1) / g_every + 1;
-        NNGP_HIP_CHECK(hipEventSynchronize(ev[2 * (size_t)(ns - 1) * g_every + 1]));
-        float total = 0.f;
-        for (int k = 0; k < ns; k++) {
-            float ms = 0.f;
-            NNGP_HIP_CHECK(hipEventElapsedTime(&ms, ev[2 * (size_t)k * g_every], ev[2 * (size_t)k * g_every + 1]));
-            total += ms;
-        }
-        *g_ms_out = total * (float)(N - I) / (float)ns;
-    }
-    return NNGP_OK;
+    return gt.finish();
 }

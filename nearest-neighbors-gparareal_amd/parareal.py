@@ -471,6 +471,9 @@ class Parareal():
                                              th0, stream)
         cs = solver.f.csystem(U1.device)
         g_ms = ctypes.c_float(0.0)
+        # every sweep entry's leading arguments: the coarse propagator, its grid, the slices, U and U_G
+        head = (ctypes.byref(cs), _lib.TABLEAU[solver.G], solver.step_mode, solver.Ng, t_dev.data_ptr(), I, N,
+                U1.data_ptr(), UG1.data_ptr())
         if isinstance(model, NNGP_p) and self._shard_corrections(model):
             return self._correction_sweep_sharded(torch, model, t_dev, I, N, U1, UG1, X, Y, rows, th0, stream)
         if isinstance(model, NNGP_p):
@@ -489,8 +492,7 @@ class Parareal():
                 self._spec_skip -= 1
                 spec = 0
             _lib.check(lib.nngp_correction_sweep(
-                ctypes.byref(cs), _lib.TABLEAU[solver.G], solver.step_mode, solver.Ng, t_dev.data_ptr(), I, N,
-                U1.data_ptr(), UG1.data_ptr(), UF.data_ptr(), UG.data_ptr(), _lib.MODEL_NNGP, X.data_ptr(),
+                *head, UF.data_ptr(), UG.data_ptr(), _lib.MODEL_NNGP, X.data_ptr(),
                 Y.data_ptr(), int(rows), m, len(jit), jp, model.n_restarts, th0.data_ptr(), float(model.fatol),
                 float(model.xatol), model.maxfev, self._preds_scratch.data_ptr(), spec,
                 ctypes.byref(hits), ctypes.byref(g_ms), stream))
@@ -503,26 +505,22 @@ class Parareal():
             Xe, Ye, He, rows_e = e.device_state()
             be, Ce = e.weights_device(U1.device)
             _lib.check(lib.nngp_elm_sweep(
-                ctypes.byref(cs), _lib.TABLEAU[solver.G], solver.step_mode, solver.Ng, t_dev.data_ptr(), I, N,
-                U1.data_ptr(), UG1.data_ptr(), Xe.data_ptr(), Ye.data_ptr(), He.data_ptr(), rows_e,
+                *head, Xe.data_ptr(), Ye.data_ptr(), He.data_ptr(), rows_e,
                 min(int(e.m), rows_e), e.poly_degree, e.N, be.data_ptr(), Ce.data_ptr(), ctypes.byref(g_ms), stream))
         elif isinstance(model, NN):
             Xn, Yn = model.device_xy()
             _lib.check(lib.nngp_knn_mean_sweep(
-                ctypes.byref(cs), _lib.TABLEAU[solver.G], solver.step_mode, solver.Ng, t_dev.data_ptr(), I, N,
-                U1.data_ptr(), UG1.data_ptr(), Xn.data_ptr(), Yn.data_ptr(), int(Xn.shape[0]),
+                *head, Xn.data_ptr(), Yn.data_ptr(), int(Xn.shape[0]),
                 min(model.nn, int(Xn.shape[0])), None, ctypes.byref(g_ms), stream))
         elif isinstance(model, GPjax_p):
             Xg, alpha, coef = model._dev
             _lib.check(lib.nngp_correction_sweep(
-                ctypes.byref(cs), _lib.TABLEAU[solver.G], solver.step_mode, solver.Ng, t_dev.data_ptr(), I, N,
-                U1.data_ptr(), UG1.data_ptr(), UF.data_ptr(), UG.data_ptr(), _lib.MODEL_GPFULL, Xg.data_ptr(),
+                *head, UF.data_ptr(), UG.data_ptr(), _lib.MODEL_GPFULL, Xg.data_ptr(),
                 alpha.data_ptr(), Xg.shape[0], 0, 0, None, 0, coef.data_ptr(), 0.0, 0.0, 0, None, 0, None,
                 ctypes.byref(g_ms), stream))
         else:
             _lib.check(lib.nngp_correction_sweep(
-                ctypes.byref(cs), _lib.TABLEAU[solver.G], solver.step_mode, solver.Ng, t_dev.data_ptr(), I, N,
-                U1.data_ptr(), UG1.data_ptr(), UF.data_ptr(), UG.data_ptr(), _lib.MODEL_PARAREAL, None, None,
+                *head, UF.data_ptr(), UG.data_ptr(), _lib.MODEL_PARAREAL, None, None,
                 0, 0, 0, None, 0, None, 0.0, 0.0, 0, None, 0, None, ctypes.byref(g_ms), stream))
         return g_ms.value / 1e3
 

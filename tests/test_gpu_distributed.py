@@ -114,11 +114,49 @@ rc_short = L.nngp_correction_sweep_sharded_emulated(
     16, 10, 9, jit.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), 1, buf.data_ptr(), 0.1, 0.1, 400,
     short.data_ptr(), short.numel(), 3, None, torch.cuda.current_stream().cuda_stream)
 assert rc_short == -1 and b"gather holds" in L.nngp_last_error(), (rc_short, L.nngp_last_error())
+# the sharded sweep's G time at its edges (0, 1, 8, 9, 17 slices, with and without g_ms_out; Lorenz split
+# over 2 emulated ranks): bitwise nngp_correction_sweep without speculation, rows <= I untouched
+lz = g.Lorenz(normalization="-11")
+ls = g.SolverRK(lz.get_vector_field(), Ng=5, Nf=50, F="RK4", G="RK1")
+lcs = ls.f.csystem(torch.device("cuda", 0))
+rng = np.random.default_rng(17)
+dv = lambda a: torch.tensor(a, dtype=torch.float64, device="cuda")
+lu0 = np.asarray(lz.get_init_cond(), dtype=np.float64)
+Xl, Yl = dv(lu0 + 0.05 * rng.standard_normal((40, 3))), dv(1e-3 * rng.standard_normal((40, 3)))
+tl, thl = dv(np.linspace(0, 0.4, 21)), dv(g.NNGP_p(n=3, N=4, nn=5, seed=3).draw_thetas(17))
+scr = torch.empty(3, dtype=torch.float64, device="cuda")
+st = torch.cuda.current_stream().cuda_stream
+gtime = []
+for n in (0, 1, 8, 9, 17):
+    runs = []
+    for which in ("plain", "sharded", "sharded, no g_ms_out"):
+        Ul = torch.full((21, 3), -7.0, dtype=torch.float64, device="cuda")
+        Ul[:4] = dv(lu0)
+        UGl = torch.full((21, 3), -7.0, dtype=torch.float64, device="cuda")
+        gm, gath = ctypes.c_float(-1.0), torch.zeros(4, dtype=torch.float64, device="cuda")
+        head = (ctypes.byref(lcs), _lib.TABLEAU["RK1"], ls.step_mode, 5, tl.data_ptr(), 3, 3 + n, Ul.data_ptr(),
+                UGl.data_ptr())
+        fit = (Xl.data_ptr(), Yl.data_ptr(), 40, 5, 9, jit.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), 1,
+               thl.data_ptr(), 0.1, 0.1, 400)
+        if which == "plain":
+            rc = L.nngp_correction_sweep(*head, None, None, _lib.MODEL_NNGP, *fit, scr.data_ptr(), 0, None,
+                                         ctypes.byref(gm), st)
+        else:
+            rc = L.nngp_correction_sweep_sharded_emulated(*head, *fit, gath.data_ptr(), 4, 2,
+                                                          ctypes.byref(gm) if which == "sharded" else None, st)
+        torch.cuda.synchronize()
+        assert rc == 0, (n, which, rc, L.nngp_last_error())
+        runs.append((Ul.cpu().numpy(), UGl.cpu().numpy(), gm.value))
+    (Up, UGp, gp_), (Us, UGs, gs_), (Un, UGn, gn_) = runs
+    gtime.append(np.array_equal(Up, Us) and np.array_equal(Up, Un) and np.array_equal(UGp, UGs)
+                 and np.array_equal(UGp, UGn) and np.all(Up[:4] == lu0) and np.all(UGp[:4] == -7.0)
+                 and np.all(np.isfinite(Up[4:4 + n])) and np.all(Up[4 + n:] == -7.0) and gn_ == -1.0
+                 and all((v == 0.0) if n == 0 else (np.isfinite(v) and v > 0.0) for v in (gp_, gs_)))
 s = g.SolverRK(ode.get_vector_field(), Ng=5, Nf=100, F="RK8", G="RK4")
 r2 = g.Parareal(ode, s, [0, 8], 16, epsilon=5e-7, verbose=None).run(model="nngp", nn=20, seed=45, early_stop=2,
                                                                   shard_corrections=True, native_comm=False)
 np.savez(sys.argv[1], k=[k0, k1, r2["k"]], same_native=np.array_equal(np.nan_to_num(u0, nan=7.0), np.nan_to_num(u1, nan=7.0)),
-         emulated=np.array(emu),
+         emulated=np.array(emu), gtime=np.array(gtime),
          same_py=np.array_equal(np.nan_to_num(u0, nan=7.0), np.nan_to_num(r2["u"], nan=7.0)),
          conv=[list(c0) == list(c1), list(c0) == list(r2["conv_int"])])
 torch.distributed.destroy_process_group()
@@ -131,6 +169,7 @@ print("comm ok")
     R = np.load(out)
     assert len(set(R['k'].tolist())) == 1 and bool(R['same_native']) and bool(R['same_py']) and all(R['conv'])
     assert R['emulated'].tolist() == [True, True, True], R['emulated']
+    assert R['gtime'].tolist() == [True] * 5, R['gtime']
 
 
 @pytest.mark.timeout(120)
