@@ -271,6 +271,32 @@ int nngp_predict(const double *X, const double *Y, int64_t rows, int d, const do
                  double *preds_out, const double *bias, double *out, double *fits_out,
                  void *stream);
 
+/* nngp_predict_batch: n_q INDEPENDENT predictions over one training set as one launch set -- the
+ * comparison nnGPs of Figure 2 at every slice's start value, or the learned correction on a grid
+ * of states.  Query q is nngp_predict(X, Y, rows, d, Q + q*d, m, ..., theta0 + q*n_fits*2, ...)
+ * bit for bit, n_fits = d*n_jitter*n_restarts: one kNN-distance launch, one select (a workgroup
+ * per query: the ordered list, y_m, D2 and kd2), all n_q*n_fits fits as one packed launch (the
+ * sweep's speculative batch, throughput-shaped) and one launch for every (query, coordinate)
+ * arg-min and posterior mean.  A query's bits depend neither on the queries beside it nor on the
+ * chunking: the host walks the queries in chunks of
+ *     min(65535, max(1, NNGP_PREDICT_BATCH_MAX_FITS / n_fits))
+ * on the stream, and the grow-only workspace (dist[nq][rows] | D2 | y_m | kd2 | fits) is sized by
+ * the chunk, never by n_q.  No host synchronisation beyond that workspace; n_q = 0 is a no-op.
+ *   Q: [n_q][d];  theta0: [n_q][n_fits][2] (query q's draws, nngp_predict's order);
+ *   preds_out: [n_q][d] = mean;  bias: [n_q][d] or NULL, out: [n_q][d] = preds + bias -- both or
+ *   neither; out may alias bias;
+ *   idx_out: int32 [n_q][m], query q's ordered list as nngp_knn gives it, or NULL;
+ *   fits_out: [n_q][n_fits][4] = (theta_x, theta_y, fval, nfev), nngp_predict's layout, or NULL.
+ *   jitter_exp_host: HOST [n_jitter].  All other arrays DEVICE.
+ * NNGP_E_ARG before any HIP call: a NULL required pointer, n_q < 0, m outside 1..min(64, rows),
+ * d < 1, n_jitter outside 1..16, n_restarts < 1, maxfev < 1, bias / out given singly.       */
+#define NNGP_PREDICT_BATCH_MAX_FITS 262144   /* fits per internal chunk; the sweep's speculation bound */
+int nngp_predict_batch(const double *X, const double *Y, int64_t rows, int d,
+                       const double *Q, int n_q, int m, int n_jitter, const double *jitter_exp_host,
+                       int n_restarts, const double *theta0, double fatol, double xatol, int maxfev,
+                       double *preds_out, const double *bias, double *out,
+                       int32_t *idx_out, double *fits_out, void *stream);
+
 /* nngp_predict_range: the coordinates [c0, c1) of nngp_predict (their fits, in the same
  * product order with their own rows of theta0 = the FULL [d*n_jitter*n_restarts][2] draws, and
  * their means) into preds_out [c1-c0]: a rank's share of one prediction when the multi-GPU

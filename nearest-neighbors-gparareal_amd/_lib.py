@@ -33,7 +33,7 @@ EXPORTS = ['nngp_abi_version', 'nngp_last_error', 'nngp_device_count', 'nngp_rk_
            'nngp_allgather_states', 'nngp_correction_sweep_sharded', 'nngp_correction_sweep_sharded_emulated',
            'nngp_elm_hidden', 'nngp_elm_predict', 'nngp_elm_sweep', 'nngp_poly_create', 'nngp_poly_destroy',
            'nngp_func_create', 'nngp_func_destroy',
-           'nngp_knn_mean', 'nngp_knn_mean_sweep']
+           'nngp_knn_mean', 'nngp_knn_mean_sweep', 'nngp_predict_batch']
 MODEL_PARAREAL, MODEL_NNGP, MODEL_GPFULL = 0, 1, 2
 
 
@@ -91,6 +91,8 @@ def lib():
     L.nngp_gp_mean.argtypes = [i32, i32, _vp, _vp, _vp, _vp, _vp, i32, _dp, _vp, _vp]
     L.nngp_predict.argtypes = [_vp, _vp, i64, i32, _vp, i32, i32, _dp, i32, _vp, dbl, dbl, i32, _vp,
                                _vp, _vp, _vp, _vp]
+    L.nngp_predict_batch.argtypes = [_vp, _vp, i64, i32, _vp, i32, i32, i32, _dp, i32, _vp, dbl, dbl, i32, _vp,
+                                     _vp, _vp, _vp, _vp, _vp]
     L.nngp_correction_sweep.argtypes = [ctypes.POINTER(CSystem), i32, i32, i64, _vp, i32, i32, _vp, _vp, _vp,
                                         _vp, i32, _vp, _vp, i64, i32, i32, _dp, i32, _vp, dbl, dbl, i32,
                                         _vp, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), _vp]

@@ -60,11 +60,13 @@ void set_error(const char *fmt, ...);
 // speculative sweep's batch buffers, which must outlive the per-slice calls.  Growing a slot
 // frees the old buffer after hipFree's implicit device synchronisation.  Not thread-safe across
 // host threads sharing a device.
-constexpr int N_WS_SLOTS = 12;   // slot 2: the sweep's speculation buffers; 3: full-GP factors; 4: fit queues; 5: parked fits;
+constexpr int N_WS_SLOTS = 14;   // slot 2: the sweep's speculation buffers; 3: full-GP factors; 4: fit queues; 5: parked fits;
                                 // 6: the re-speculation window's batch (slot 1 may still be read by an overlapped batch);
                                 // 7 / 8: the fit queues of the overlapped batch / of the re-speculation window;
                                 // 9: the sharded sweep's zeros (nngp_comm.hip);
                                 // 10 / 11: the ELM prediction's scratch / nngp_elm_hidden's partial sums (nngp_elm.hip)
+                                // 12 / 13: nngp_predict_batch's chunk workspace / its fit queues
+constexpr int WS_PREDICT_BATCH = 12, WS_PREDICT_BATCH_QUEUE = 13;
 void *workspace(size_t bytes, int *err, int slot = 0);
 
 // Table-backed vector fields: the library's registry of term tables (nngp_table.hip).
@@ -227,9 +229,16 @@ int predict_impl(const TrainSet &T, const FitSet &F, const double *new_x, const 
                  const HitMean *hm = nullptr, hipEvent_t bias_ready = nullptr);
 int gpfull_mean(const double *X, int64_t rows, int d, const double *q, const double *coef, const double *alpha,
                 const double *bias, double *out, hipStream_t st);
+// bo: the queries are independent predictions to finish here (nngp_predict_batch) -- the select also
+// writes each query's kd2, and one more launch gives every (query, coordinate) arg-min and mean;
+// idx_out / fits_out may then be null (the slot's workspace holds them)
+struct BatchOut {   // [nq][d] each: preds = mean, out = mean + bias (both or neither; out may alias bias)
+    double *preds; const double *bias; double *out;
+};
 int spec_batch(const TrainSet &T, const FitSet &F, const double *Q, int nq, const double *theta0, int32_t *idx_out,
                double *fits_out, bool latency, hipStream_t st, int slot = 1, int32_t *done = nullptr,
-               hipEvent_t ev_select = nullptr, double *pre_AP = nullptr, int32_t *pre_done = nullptr);
+               hipEvent_t ev_select = nullptr, double *pre_AP = nullptr, int32_t *pre_done = nullptr,
+               const BatchOut *bo = nullptr);
 // gp_pre_kernel's workgroups per prediction (the HitMean target) for d coordinates at fit size m
 int pre_target(int d, int m);
 int pre_maxm(int m);   // the padded fit size of m

@@ -22,6 +22,8 @@
 //                      coordinate does the arg-min, the posterior mean and u = mean + uG
 //                      (parareal.py:382).  Used when the fits would oversubscribe the SIMDs.
 //   gp_mean_kernel<MAXM>  arg-min (from a fits array) or given (theta, jitter), posterior mean.
+//   gp_mean_batch_kernel<MAXM>  the same for every prediction of a batch of independent queries
+//                      (nngp_predict_batch; blockIdx.y = query).
 // A likelihood evaluation (gp_factor/gp_nlml): lane l of a fit's row holds rows l (and l+16) of
 // the m x m kernel matrix, padded to MAXM in {8,16,24,32} with exact identity rows; the triangle's
 // exps are spread over the 16 lanes through an LDS image; the Cholesky / solve broadcasts are
@@ -897,6 +899,23 @@ __global__ void __launch_bounds__(WGT<MAXM>::T) gp_mean_kernel(NMArgs a) {
     gp_mean_dev<MAXM>(a, blockIdx.x, true);
 }
 
+// gp_mean_kernel for every prediction of a batch of independent queries (nngp_predict_batch):
+// blockIdx.y = prediction, blockIdx.x = its workgroup of coordinates.  D2, y_m and the fits move by
+// the batch's strides as in the fits kernels (nm_batch_offsets); kd2 [nq][m], preds, bias and out
+// [nq][d] are dense.  The arg-min and the mean are gp_mean_dev itself, so a prediction's bits are
+// gp_mean_kernel's on the same D2, kd2, y_m and fits.  (out may alias bias: a lane reads
+// bias[q][c] before it writes out[q][c], and no other lane touches either.)
+template <int MAXM>
+__global__ void __launch_bounds__(WGT<MAXM>::T) gp_mean_batch_kernel(NMArgs a) {
+    nm_batch_offsets(a);
+    const int64_t q = blockIdx.y;
+    a.kd2 += q * a.m;
+    a.preds += q * a.d;
+    if (a.bias) a.bias += q * a.d;
+    if (a.out) a.out += q * a.d;
+    gp_mean_dev<MAXM>(a, blockIdx.x, true);
+}
+
 // The query-independent half of gp_mean_dev for every coordinate of a speculative batch's
 // predictions (blockIdx.y = prediction, batched offsets as the fits kernels): the first arg-min
 // over the prediction's fits, then gp_mean_prep.  AP[q][c] = alpha rows 0..MAXM-1 | c | psy | ok
@@ -1285,13 +1304,18 @@ static int launch_nm(NMArgs &a, bool fused, int nblocks, int threads, size_t lds
     return NNGP_OK;
 }
 
-static int run_mean(NMArgs &a, hipStream_t st) {
+// nq = 0: one prediction (gp_mean_kernel); nq >= 1: a batch's nq predictions, a.qs_* its strides
+// (gp_mean_batch_kernel, prediction = blockIdx.y <= 65535)
+static int run_mean(NMArgs &a, hipStream_t st, int nq = 0) {
     const int maxm = maxm_for(a.m);
     const int threads = wg_threads(maxm), per = threads / 16;
     const size_t lds = sizeof(double) * ((size_t)a.m * a.m + a.m + (size_t)per * k_image_doubles(maxm));
-    const dim3 grid((a.d + per - 1) / per);
+    const dim3 grid((a.d + per - 1) / per, nq > 0 ? nq : 1);
     return with_maxm(a.m, [&](auto mc) {
-        hipLaunchKernelGGL(gp_mean_kernel<decltype(mc)::value>, grid, dim3(threads), lds, st, a);
+        if (nq > 0)
+            hipLaunchKernelGGL(gp_mean_batch_kernel<decltype(mc)::value>, grid, dim3(threads), lds, st, a);
+        else
+            hipLaunchKernelGGL(gp_mean_kernel<decltype(mc)::value>, grid, dim3(threads), lds, st, a);
         NNGP_LAUNCH_CHECK();
         return NNGP_OK;
     });
@@ -1713,9 +1737,12 @@ static int run_pre(const NMArgs &p, double *AP, int32_t *pre_done, int nq, hipSt
 // prediction's own theta0 draws (theta0[nq][n_fits][2]).  One kNN-distance launch, one
 // kNN-select launch (a workgroup per query) and ONE packed fits launch (4 fits per wave over
 // all nq*n_fits fits) -- the throughput-shaped work that the sequential sweep then only looks up.
+// With bo the queries are independent predictions (nngp_predict_batch): the select / D2 launches
+// also write kd2[nq][m] and gp_mean_batch_kernel finishes every prediction; D2, y_m and the fits
+// are what they are without it.
 int spec_batch(const TrainSet &T, const FitSet &F, const double *Q, int nq, const double *theta0, int32_t *idx_out,
                double *fits_out, bool latency, hipStream_t st, int slot, int32_t *done, hipEvent_t ev_select,
-               double *pre_AP, int32_t *pre_done) {
+               double *pre_AP, int32_t *pre_done, const BatchOut *bo) {
     const double *X = T.X, *Y = T.Y;
     const int64_t rows = T.rows;
     const int d = T.d, m = F.m;
@@ -1724,13 +1751,21 @@ int spec_batch(const TrainSet &T, const FitSet &F, const double *Q, int nq, cons
     int rc = fill_jitters(a, F.n_jitter, F.jitter_exp_host);
     if (rc) return rc;
     const size_t nfp = (size_t)F.n_fits(d);
-    // slot-1 workspace: dist[nq][rows] | D2[nq][m*m] | ymT[nq][d*m]
+    // the slot's workspace: dist[nq][rows] | D2[nq][m*m] | ymT[nq][d*m], and with bo (independent
+    // queries finished here, no sweep behind them) | kd2[nq][m] | the fits and the lists the caller
+    // did not ask for (fits[nq][n_fits][4], idx[nq][m])
     int err = 0;
-    double *dist = (double *)workspace(sizeof(double) * (size_t)nq * ((size_t)rows + (size_t)m * m + (size_t)d * m),
+    const size_t base_doubles = (size_t)nq * ((size_t)rows + (size_t)m * m + (size_t)d * m);
+    const size_t kd2_doubles = bo ? (size_t)nq * m : 0, fits_doubles = (bo && !fits_out) ? (size_t)nq * nfp * 4 : 0;
+    double *dist = (double *)workspace(sizeof(double) * (base_doubles + kd2_doubles + fits_doubles) +
+                                           ((bo && !idx_out) ? sizeof(int32_t) * (size_t)nq * m : 0),
                                        &err, slot);
     if (err) return err;
     double *D2 = dist + (size_t)nq * rows;
     double *ymT = D2 + (size_t)nq * m * m;
+    double *kd2 = bo ? dist + base_doubles : nullptr;
+    if (bo && !fits_out) fits_out = dist + base_doubles + kd2_doubles;
+    if (bo && !idx_out) idx_out = (int32_t *)(dist + base_doubles + kd2_doubles + fits_doubles);
     if (done) NNGP_HIP_CHECK(hipMemsetAsync(done, 0, sizeof(int32_t) * (size_t)nq, st));
     if (pre_AP) NNGP_HIP_CHECK(hipMemsetAsync(pre_done, 0, sizeof(int32_t) * (size_t)nq, st));
     hipLaunchKernelGGL(knn_dist_kernel, dim3((unsigned)((rows + 63) / 64), (unsigned)nq), dim3(64), 0, st, X,
@@ -1738,18 +1773,22 @@ int spec_batch(const TrainSet &T, const FitSet &F, const double *Q, int nq, cons
     NNGP_LAUNCH_CHECK();
     const bool wave_d2 = d2_by_waves(m, d), pair_d2 = d2_by_pairs(m, d);
     launch_knn_select(dim3(1, (unsigned)nq), knn_xs_bytes(m, d), st, dist, rows, m, X, Y, d, Q, idx_out,
-                      (double *)nullptr, ymT, (wave_d2 || pair_d2) ? (double *)nullptr : D2, (double *)nullptr,
+                      (double *)nullptr, ymT, (wave_d2 || pair_d2) ? (double *)nullptr : D2,
+                      (wave_d2 || pair_d2) ? (double *)nullptr : kd2,
                       (const int32_t *)nullptr, (int32_t *)nullptr, knn_xs_doubles(m, d), (const int32_t *)nullptr,
                       (int32_t *)nullptr, HitMean{});
     NNGP_LAUNCH_CHECK();
+    // (the sweep's batches want no kd2 -- each slice's own select gives it -- and their grids are
+    // the pairs alone; with kd2 its m rows are the next m tasks, as in predict_impl)
+    const int d2_tasks = m * (m + 1) / 2 + (kd2 ? m : 0);
     if (wave_d2) {
-        hipLaunchKernelGGL(d2_wave_kernel, dim3((unsigned)(m * (m + 1) / 2), (unsigned)nq), dim3(64), 0, st, X,
-                           idx_out, m, d, Q, D2, (double *)nullptr);
+        hipLaunchKernelGGL(d2_wave_kernel, dim3((unsigned)d2_tasks, (unsigned)nq), dim3(64), 0, st, X,
+                           idx_out, m, d, Q, D2, kd2);
         NNGP_LAUNCH_CHECK();
     }
     if (pair_d2) {
-        hipLaunchKernelGGL(d2_pairs_kernel, dim3((unsigned)((m * (m + 1) / 2 + 255) / 256), (unsigned)nq), dim3(256), 0,
-                           st, X, idx_out, m, d, Q, D2, (double *)nullptr);
+        hipLaunchKernelGGL(d2_pairs_kernel, dim3((unsigned)((d2_tasks + 255) / 256), (unsigned)nq), dim3(256), 0,
+                           st, X, idx_out, m, d, Q, D2, kd2);
         NNGP_LAUNCH_CHECK();
     }
     // the counters are zeroed (above) before the event the sweep's mean kernels wait behind
@@ -1765,8 +1804,15 @@ int spec_batch(const TrainSet &T, const FitSet &F, const double *Q, int nq, cons
     // latency: a wave per fit (the re-speculation window the sweep waits on); else packed fits.
     // (The window on the packed or the 4-lanes kernel: Burgers 0.297 / 0.281 s against 0.221 s,
     // profiles/r05/nm_lanes/respec_shape_not_kept.txt -- the next slice waits on its slowest fit.)
-    rc = latency ? run_nm_spec(a, st, nq) : run_nm(a, false, st, nq, slot == 1 ? 7 : 8);
-    if (rc || !pre_AP) return rc;
+    const int qslot = slot == 1 ? 7 : (slot == WS_PREDICT_BATCH ? WS_PREDICT_BATCH_QUEUE : 8);
+    rc = latency ? run_nm_spec(a, st, nq) : run_nm(a, false, st, nq, qslot);
+    if (rc) return rc;
+    if (bo) {   // every (query, coordinate) arg-min and posterior mean, one launch
+        NMArgs mb = p;
+        mb.kd2 = kd2; mb.preds = bo->preds; mb.bias = bo->bias; mb.out = bo->out;
+        return run_mean(mb, st, nq);
+    }
+    if (!pre_AP) return rc;
     return run_pre(p, pre_AP, pre_done, nq, st);
 }
 
@@ -2113,6 +2159,50 @@ extern "C" int nngp_predict(const double *X, const double *Y, int64_t rows, int 
                             void *stream) {
     return nngp::predict_impl({X, Y, rows, d}, {m, n_jitter, jitter_exp_host, n_restarts, fatol, xatol, maxfev}, new_x,
                               theta0, {preds_out, bias, out, fits_out}, SpecRefs{}, (hipStream_t)stream, 0, d);
+}
+
+// queries per chunk of nngp_predict_batch: the fits bound, and blockIdx.y's range
+static int64_t predict_batch_chunk(int64_t n_fits) {
+    return std::min<int64_t>(65535, std::max<int64_t>(1, NNGP_PREDICT_BATCH_MAX_FITS / n_fits));
+}
+
+extern "C" int nngp_predict_batch(const double *X, const double *Y, int64_t rows, int d, const double *Q, int n_q,
+                                  int m, int n_jitter, const double *jitter_exp_host, int n_restarts,
+                                  const double *theta0, double fatol, double xatol, int maxfev, double *preds_out,
+                                  const double *bias, double *out, int32_t *idx_out, double *fits_out,
+                                  void *stream) {
+    NNGP_REQUIRE(X != nullptr, "X is NULL");
+    NNGP_REQUIRE(Y != nullptr, "Y is NULL");
+    NNGP_REQUIRE(Q != nullptr, "Q is NULL");
+    NNGP_REQUIRE(jitter_exp_host != nullptr, "jitter_exp_host is NULL");
+    NNGP_REQUIRE(theta0 != nullptr, "theta0 is NULL");
+    NNGP_REQUIRE(preds_out != nullptr, "preds_out is NULL");
+    NNGP_REQUIRE((bias == nullptr) == (out == nullptr), "bias and out are given both or neither");
+    NNGP_REQUIRE(n_q >= 0, "n_q must be >= 0 (got %d)", n_q);
+    NNGP_REQUIRE(d >= 1, "d must be >= 1 (got %d)", d);
+    NNGP_REQUIRE(m >= 1 && m <= MAX_M && m <= rows, "need 1 <= m <= min(%d, rows) (m=%d rows=%lld)", MAX_M, m,
+                 (long long)rows);
+    NNGP_REQUIRE(n_jitter >= 1 && n_jitter <= MAX_JIT, "n_jitter must be in [1, %d] (got %d)", MAX_JIT, n_jitter);
+    NNGP_REQUIRE(n_restarts >= 1, "n_restarts must be >= 1 (got %d)", n_restarts);
+    NNGP_REQUIRE(maxfev >= 1, "maxfev must be >= 1 (got %d)", maxfev);
+    const int64_t n_fits = (int64_t)d * n_jitter * n_restarts;
+    NNGP_REQUIRE(n_fits <= INT32_MAX / 4, "d * n_jitter * n_restarts = %lld fits per query is too many",
+                 (long long)n_fits);
+    if (n_q == 0) return NNGP_OK;
+    const TrainSet T{X, Y, rows, d};
+    const FitSet F{m, n_jitter, jitter_exp_host, n_restarts, fatol, xatol, maxfev};
+    // chunks on the stream, one after the other through the same chunk-sized workspace (the first
+    // chunk is the largest); a query's launches see its own rows of every array only
+    const int64_t chunk = predict_batch_chunk(n_fits);
+    for (int64_t q0 = 0; q0 < n_q; q0 += chunk) {
+        const int nq = (int)std::min<int64_t>(chunk, n_q - q0);
+        const BatchOut bo{preds_out + q0 * d, bias ? bias + q0 * d : nullptr, out ? out + q0 * d : nullptr};
+        const int rc = spec_batch(T, F, Q + q0 * d, nq, theta0 + q0 * n_fits * 2, idx_out ? idx_out + q0 * m : nullptr,
+                                  fits_out ? fits_out + q0 * n_fits * 4 : nullptr, false, (hipStream_t)stream,
+                                  WS_PREDICT_BATCH, nullptr, nullptr, nullptr, nullptr, &bo);
+        if (rc) return rc;
+    }
+    return NNGP_OK;
 }
 
 extern "C" int nngp_predict_range(const double *X, const double *Y, int64_t rows, int d, const double *new_x,

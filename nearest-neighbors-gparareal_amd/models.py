@@ -11,6 +11,8 @@ numpy's Lemire sampler never rejects; pinned by tests/test_host.py against tests
 Compute paths (all HIP, no CPU fallback):
   predict(...)         reference signature, host arrays in/out -> nngp_predict (fused kernels)
   predict_device(...)  device tensors, used by the Parareal driver's sequential loop
+  predict_batch(...) / predict_batch_device(...)  many independent queries -> nngp_predict_batch,
+                       each bitwise its predict (the driver's model comparison)
   get_preds(...)       reference signature on pre-selected (xm, ym) -> nngp_nm_fit_batch +
                        first-argmin + nngp_gp_mean (the unfused path of the same kernels)
 
@@ -210,15 +212,67 @@ class NNGP_p(ModelAbstr):
         self.train_count += self.n_fits
         return preds
 
-    # ------------------------------------------------------------------------- reference API
-    def predict(self, new_x, prev_F=None, prev_G=None, *args, **kwargs):
-        """models.py:171-183 (host arrays in/out; kNN + fits + argmin + mean on the GPU)."""
-        torch = _lib.require_gpu()
-        if self._dev_xy is None:   # fit() was given host arrays (or x / y were assigned)
+    def device_xy(self):
+        """(X, Y) on the device, uploading a host training set given to fit() (or assigned)."""
+        if self._dev_xy is None:
             if self._host_xy is None or self._host_xy[0] is None or self._host_xy[1] is None:
                 raise AttributeError("'NNGP_p' has no training set yet: call fit(x, y, k) first")
             self._dev_xy = (_lib.as_device(self._host_xy[0]), _lib.as_device(self._host_xy[1]))
-        X, Y = self._dev_xy
+        return self._dev_xy
+
+    def predict_batch_device(self, Q, theta0=None, out=None, bias=None, preds=None, idx_out=None, fits_out=None,
+                             stream=None):
+        """Independent corrections at every row of Q [nq][n] on the model's device training set, one
+        launch set (nngp_predict_batch): row q is predict_device(X, Y, rows, Q[q], theta0[q]) bit
+        for bit.  theta0: [nq][n_fits][2] (or [nq * n_fits][2]); None draws it here -- the RNG stream
+        of nq consecutive predict calls.  Writes preds [nq][n] (and out = preds + bias, given
+        together; out may be bias itself), optionally idx_out int32 [nq][m] (the ordered neighbour
+        lists) and fits_out [nq][n_fits][4]."""
+        import torch
+        X, Y = self.device_xy()
+        rows, n = int(X.shape[0]), self.n
+        if X.dim() != 2 or int(X.shape[1]) != n or rows < 1:
+            raise ValueError(f'the training set must be [rows >= 1][{n}] (got x of shape {tuple(X.shape)})')
+        _knn_tensor(X, 'x', X.shape, X.device)
+        _knn_tensor(Y, 'y', X.shape, X.device)
+        m = min(self.n_neighbours(), rows)   # argsort(...)[:nn] on fewer rows keeps them all
+        if not torch.is_tensor(Q) or Q.dim() != 2:
+            raise ValueError('Q must be a device tensor of shape [n_q][n]')
+        nq, nf = int(Q.shape[0]), self.n_fits
+        q_ptr = _knn_tensor(Q, 'Q', (nq, n), X.device)
+        if (out is None) != (bias is None):
+            raise ValueError('out and bias go together')
+        if theta0 is None:
+            theta0 = torch.tensor(self.draw_thetas(nq), dtype=torch.float64, device=X.device)
+        flat = torch.is_tensor(theta0) and tuple(theta0.shape) == (nq * nf, 2)
+        th_ptr = _knn_tensor(theta0, 'theta0', (nq * nf, 2) if flat else (nq, nf, 2), X.device)
+        if preds is None:
+            preds = torch.empty((nq, n), dtype=torch.float64, device=X.device)
+        if nq == 0:   # (an empty tensor has no address to hand over)
+            return preds
+        ptr = lambda t, name, shape, dtype=None: None if t is None else _knn_tensor(t, name, shape, X.device, dtype)
+        jit, jp = _lib.host_doubles(JITTERS)
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().nngp_predict_batch(
+            X.data_ptr(), Y.data_ptr(), rows, n, q_ptr, nq, m, len(jit), jp, self.n_restarts, th_ptr,
+            float(self.fatol), float(self.xatol), self.maxfev, ptr(preds, 'preds', (nq, n)),
+            ptr(bias, 'bias', (nq, n)), ptr(out, 'out', (nq, n)), ptr(idx_out, 'idx_out', (nq, m), torch.int32),
+            ptr(fits_out, 'fits_out', (nq, nf, 4)), st))
+        self.train_count += nq * nf
+        return preds
+
+    # ------------------------------------------------------------------------- reference API
+    def predict_batch(self, new_x):
+        """predict at every row of new_x [nq][n] (host arrays in/out): what nq consecutive predict
+        calls return, RNG stream included, as one launch set."""
+        torch = _lib.require_gpu()
+        Q = torch.tensor(np.ascontiguousarray(np.asarray(new_x, dtype=np.float64).reshape(-1, self.n)), device='cuda')
+        return self.predict_batch_device(Q).cpu().numpy()
+
+    def predict(self, new_x, prev_F=None, prev_G=None, *args, **kwargs):
+        """models.py:171-183 (host arrays in/out; kNN + fits + argmin + mean on the GPU)."""
+        torch = _lib.require_gpu()
+        X, Y = self.device_xy()
         q = torch.tensor(np.asarray(new_x, dtype=np.float64).reshape(-1), device='cuda')
         th0 = torch.tensor(self.draw_thetas(1), device='cuda')
         preds = self.predict_device(X, Y, X.shape[0], q, th0)

@@ -639,8 +639,8 @@ class Parareal():
         comp_mdls at every slice's actual starting value U1[i], i = I..N-1, after the sweep.  The
         queries are independent of each other (nothing here feeds back into the iterate), so all NN
         models share ONE nngp_knn_mean launch (their counts as the list, groups of 16); an NNGP_p
-        predicts slice by slice with its own draws (its RNG stream is the reference's: one model,
-        slices in order), GPjax_p / ELM through predict_device, any other ModelAbstr through its
+        predicts all slices as one nngp_predict_batch with its own draws (its RNG stream is the
+        reference's: one model, slices in order; bitwise the slice-by-slice predictions), GPjax_p / ELM through predict_device, any other ModelAbstr through its
         predict on host arrays.  Returns {id(model): predictions [N-I][n] on the host}."""
         n, nq = self.n, N - I
         Q = U1[I:N]
@@ -658,11 +658,8 @@ class Parareal():
             if isinstance(m, (NNGP_p, GPjax_p, ELM)):
                 P = torch.empty((nq, n), dtype=torch.float64, device=U1.device)
                 if isinstance(m, NNGP_p):
-                    X, Y = m._dev_xy
-                    nf = m.n_fits
                     th0 = torch.tensor(m.draw_thetas(nq), dtype=torch.float64, device=U1.device)
-                    for j in range(nq):
-                        m.predict_device(X, Y, X.shape[0], Q[j], th0[j * nf:(j + 1) * nf], preds=P[j], stream=stream)
+                    m.predict_batch_device(Q, theta0=th0, preds=P, stream=stream)
                 elif isinstance(m, GPjax_p):
                     for j in range(nq):
                         m.predict_device(Q[j], out=P[j], stream=stream)
