@@ -297,6 +297,50 @@ int nngp_predict_batch(const double *X, const double *Y, int64_t rows, int d,
                        double *preds_out, const double *bias, double *out,
                        int32_t *idx_out, double *fits_out, void *stream);
 
+/* nngp_predict_listed: nngp_predict_batch with each query's kNN replaced by a PRESCRIBED ordered
+ * neighbour list, lists_host[q][0..m) (the nntype variants of the reference's NNGP_alt,
+ * nnGPara_with_time.py:50-171, choose neighbours by their place in the (interval, iteration) table
+ * instead of by distance).  No distance launch and no select: one gather of y_m^T per query, D2 and
+ * kd2 per query (a wave per pair where nngp_predict's dispatch uses waves, else a thread per pair;
+ * every form gives the same bits), all n_q*n_fits fits as one packed launch and one launch for every
+ * (query, coordinate) arg-min and posterior mean, in nngp_predict_batch's chunks.
+ *   lists_host: HOST int32 [n_q][m].  Every entry is checked against [0, rows) before any HIP call
+ *   and the library uploads the lists itself, so a bad list is NNGP_E_ARG, never a device fault (in
+ *   pinned memory the upload is asynchronous: keep it until the stream has passed the call).  A row
+ *   may appear more than once; the fits then see what the reference's see on a duplicated row.
+ *   Q, theta0, preds_out, bias, out, fits_out and the refusals: as nngp_predict_batch.
+ * Contract: where lists_host[q] is what nngp_knn returns for Q[q], query q's preds_out, out and
+ * fits_out are nngp_predict's bit for bit. */
+int nngp_predict_listed(const double *X, const double *Y, int64_t rows, int d, const double *Q, int n_q,
+                        const int32_t *lists_host, int m, int n_jitter, const double *jitter_exp_host,
+                        int n_restarts, const double *theta0, double fatol, double xatol, int maxfev,
+                        double *preds_out, const double *bias, double *out, double *fits_out,
+                        void *stream);
+
+/* nngp_listed_sweep: the sequential sweep of one iteration on prescribed lists: for i = I .. N-1
+ *     UG1[i+1] = G(t[i], t[i+1], U1[i])
+ *     U1[i+1]  = mean_i(U1[i]) + UG1[i+1],   preds_out[i-I] = mean_i(U1[i])
+ * with mean_i the listed prediction on lists_host[i-I] with the draws theta0[i-I].  A list does not
+ * depend on the query, so nothing of a fit does: before the chain, for all N-I slices at once, the
+ * gather and D2, ONE packed fits launch and ONE launch that prepares every (slice, coordinate)
+ * (alpha, the kernel scalars, the factorisation's success).  What is left per slice is G, m
+ * distances, d short dot products and the add:
+ *   - one-wave form (every ODE kind; Burgers with d = 64k <= 256; exact G): the whole chain is ONE
+ *     launch of one 64-lane workgroup.  *g_ms_out is 0 in this form: the G time is not separated.
+ *   - launch form (everything else: field kernels, tables, larger Burgers, NNGP_STEP_CONTRACT): per
+ *     slice the G launch and one mean launch (for d > 128 a kd2 launch between them); *g_ms_out as
+ *     in nngp_elm_sweep.
+ * Both forms give the bits of a per-slice loop of nngp_rk_batch, nngp_predict_listed with n_q = 1
+ * and the update.  All on `stream`, no host synchronisation beyond the grow-only workspace.
+ *   t, U1, UG1 as in nngp_correction_sweep; lists_host: HOST int32 [N-I][m], checked and uploaded as
+ *   in nngp_predict_listed; theta0: DEVICE [N-I][n_fits][2]; preds_out: DEVICE [N-I][d] or NULL;
+ *   g_ms_out: HOST or NULL.  N <= I is a no-op.  Refusals as nngp_predict_listed. */
+int nngp_listed_sweep(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t g_steps,
+                      const double *t, int I, int N, double *U1, double *UG1, const double *X,
+                      const double *Y, int64_t rows, const int32_t *lists_host, int m, int n_jitter,
+                      const double *jitter_exp_host, int n_restarts, const double *theta0, double fatol,
+                      double xatol, int maxfev, double *preds_out, float *g_ms_out, void *stream);
+
 /* nngp_predict_range: the coordinates [c0, c1) of nngp_predict (their fits, in the same
  * product order with their own rows of theta0 = the FULL [d*n_jitter*n_restarts][2] draws, and
  * their means) into preds_out [c1-c0]: a rank's share of one prediction when the multi-GPU

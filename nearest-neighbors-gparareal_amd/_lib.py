@@ -33,7 +33,7 @@ EXPORTS = ['nngp_abi_version', 'nngp_last_error', 'nngp_device_count', 'nngp_rk_
            'nngp_allgather_states', 'nngp_correction_sweep_sharded', 'nngp_correction_sweep_sharded_emulated',
            'nngp_elm_hidden', 'nngp_elm_predict', 'nngp_elm_sweep', 'nngp_poly_create', 'nngp_poly_destroy',
            'nngp_func_create', 'nngp_func_destroy',
-           'nngp_knn_mean', 'nngp_knn_mean_sweep', 'nngp_predict_batch']
+           'nngp_knn_mean', 'nngp_knn_mean_sweep', 'nngp_predict_batch', 'nngp_predict_listed', 'nngp_listed_sweep']
 MODEL_PARAREAL, MODEL_NNGP, MODEL_GPFULL = 0, 1, 2
 
 
@@ -130,6 +130,11 @@ def lib():
     L.nngp_knn_mean.argtypes = [_vp, _vp, i64, i32, _vp, i32, _ip, i32, _vp, _vp, _vp, _vp, _vp]
     L.nngp_knn_mean_sweep.argtypes = [ctypes.POINTER(CSystem), i32, i32, i64, _vp, i32, i32, _vp, _vp, _vp, _vp, i64,
                                       i32, _vp, ctypes.POINTER(ctypes.c_float), _vp]
+    L.nngp_predict_listed.argtypes = [_vp, _vp, i64, i32, _vp, i32, _vp, i32, i32, _dp, i32, _vp, dbl, dbl, i32, _vp,
+                                      _vp, _vp, _vp, _vp]
+    L.nngp_listed_sweep.argtypes = [ctypes.POINTER(CSystem), i32, i32, i64, _vp, i32, i32, _vp, _vp, _vp, _vp, i64,
+                                    _vp, i32, i32, _dp, i32, _vp, dbl, dbl, i32, _vp, ctypes.POINTER(ctypes.c_float),
+                                    _vp]
     for name in EXPORTS:
         if name not in ('nngp_abi_version', 'nngp_last_error', 'nngp_device_count', 'nngp_chain_stats',
                         'nngp_sweep_late_reruns'):

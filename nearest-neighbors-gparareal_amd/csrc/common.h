@@ -60,13 +60,14 @@ void set_error(const char *fmt, ...);
 // speculative sweep's batch buffers, which must outlive the per-slice calls.  Growing a slot
 // frees the old buffer after hipFree's implicit device synchronisation.  Not thread-safe across
 // host threads sharing a device.
-constexpr int N_WS_SLOTS = 14;   // slot 2: the sweep's speculation buffers; 3: full-GP factors; 4: fit queues; 5: parked fits;
+constexpr int N_WS_SLOTS = 15;   // slot 2: the sweep's speculation buffers; 3: full-GP factors; 4: fit queues; 5: parked fits;
                                 // 6: the re-speculation window's batch (slot 1 may still be read by an overlapped batch);
                                 // 7 / 8: the fit queues of the overlapped batch / of the re-speculation window;
                                 // 9: the sharded sweep's zeros (nngp_comm.hip);
                                 // 10 / 11: the ELM prediction's scratch / nngp_elm_hidden's partial sums (nngp_elm.hip)
-                                // 12 / 13: nngp_predict_batch's chunk workspace / its fit queues
-constexpr int WS_PREDICT_BATCH = 12, WS_PREDICT_BATCH_QUEUE = 13;
+                                // 12 / 13: nngp_predict_batch's and nngp_predict_listed's chunk workspace / fit queues
+                                // 14: nngp_listed_sweep's prepared coordinates, lists and kd2 (live through the sweep)
+constexpr int WS_PREDICT_BATCH = 12, WS_PREDICT_BATCH_QUEUE = 13, WS_LISTED_SWEEP = 14;
 void *workspace(size_t bytes, int *err, int slot = 0);
 
 // Table-backed vector fields: the library's registry of term tables (nngp_table.hip).

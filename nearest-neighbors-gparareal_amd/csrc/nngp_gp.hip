@@ -42,6 +42,7 @@
 #include "nngp_nm.h"
 #include "nngp_nmargs.h"
 #include "nngp_knn_dev.h"
+#include "nngp_listed_host.h"
 #include "tableau.h"
 
 namespace nngp {
@@ -188,18 +189,14 @@ __global__ void __launch_bounds__(256) d2_pairs_kernel(const double *__restrict_
 // terms here), their values to LDS, and lane 0 combines them in the recursion's order: bitwise
 // pw_sqdiff, with 64 lanes and all loads in flight instead of one lane walking d terms
 // (FHN-PDE d = 800, m = 20: 230 such sums per prediction).
-__global__ void __launch_bounds__(64) d2_wave_kernel(const double *__restrict__ X, const int32_t *__restrict__ idx,
-                                                     int m, int d, const double *__restrict__ q,
-                                                     double *__restrict__ D2, double *__restrict__ kd2) {
+// task t of one query by the calling wave: pair t < m(m+1)/2, else kd2 row t - m(m+1)/2
+__device__ __forceinline__ void d2_wave_task(const double *__restrict__ X, const int32_t *__restrict__ idx, int m,
+                                             int d, const double *__restrict__ q, double *__restrict__ D2,
+                                             double *__restrict__ kd2, int t) {
     __shared__ double leafv[16];
     __shared__ int leafo[16], leafl[16];
     __shared__ int nleaf;
-    const int qy = blockIdx.y;
-    idx += (size_t)qy * m;
-    q += (size_t)qy * d;
-    D2 += (size_t)qy * m * m;
-    if (kd2) kd2 += (size_t)qy * m;
-    const int t = blockIdx.x, lane = threadIdx.x;
+    const int lane = threadIdx.x;
     const int npairs = m * (m + 1) / 2;
     int r = 0, j = 0;
     const bool is_kd = t >= npairs;
@@ -243,6 +240,22 @@ __global__ void __launch_bounds__(64) d2_wave_kernel(const double *__restrict__ 
             D2[j * m + r] = v;
         }
     }
+}
+
+__global__ void __launch_bounds__(64) d2_wave_kernel(const double *__restrict__ X, const int32_t *__restrict__ idx,
+                                                     int m, int d, const double *__restrict__ q,
+                                                     double *__restrict__ D2, double *__restrict__ kd2) {
+    const int qy = blockIdx.y;
+    d2_wave_task(X, idx + (size_t)qy * m, m, d, q + (size_t)qy * d, D2 + (size_t)qy * m * m,
+                 kd2 ? kd2 + (size_t)qy * m : nullptr, blockIdx.x);
+}
+
+// the kd2 tasks alone (a listed sweep's slice: its D2 went into the prepared coordinates): block r is
+// d2_wave_kernel's block m(m+1)/2 + r
+__global__ void __launch_bounds__(64) kd2_wave_kernel(const double *__restrict__ X, const int32_t *__restrict__ idx,
+                                                      int m, int d, const double *__restrict__ q,
+                                                      double *__restrict__ kd2) {
+    d2_wave_task(X, idx, m, d, q, nullptr, kd2, m * (m + 1) / 2 + (int)blockIdx.x);
 }
 
 // D2 / kd2 from an explicit xm (unfused entry points)
@@ -1732,6 +1745,20 @@ static int run_pre(const NMArgs &p, double *AP, int32_t *pre_done, int nq, hipSt
     });
 }
 
+// the packed fits' arguments of a batch of predictions (a: jitters filled): per prediction
+// D2[m][m], y_m^T[d][m], theta0[n_fits][2] and fits[n_fits][4], dense, back to back
+static void batch_fit_args(NMArgs &a, const FitSet &F, int d, const double *D2, const double *ymT,
+                           const double *theta0, double *fits_out) {
+    const int m = F.m;
+    const int64_t nfp = F.n_fits(d);
+    a.m = m; a.d = d; a.n_fits = (int)nfp;
+    a.D2 = D2; a.Y = ymT; a.ys_c = m; a.ys_r = 1;
+    a.theta0 = theta0; a.fatol = F.fatol; a.xatol = F.xatol; a.maxfev = F.maxfev; a.R = F.n_restarts;
+    a.fits_out = fits_out;
+    a.qs_D2 = (int64_t)m * m; a.qs_Y = (int64_t)d * m; a.qs_th = nfp * 2; a.qs_fits = nfp * 4;
+    a.jmajor = env_int("NNGP_NM_JMAJOR", 1);   // (run_nm_parked; Burgers 0.328 -> 0.317 s)
+}
+
 // The speculative batch: for nq guessed queries Q[nq][d] at once, the ordered kNN lists
 // (idx_out[nq][m]) and every fit of every prediction (fits_out[nq][n_fits][4]), with each
 // prediction's own theta0 draws (theta0[nq][n_fits][2]).  One kNN-distance launch, one
@@ -1793,12 +1820,7 @@ int spec_batch(const TrainSet &T, const FitSet &F, const double *Q, int nq, cons
     }
     // the counters are zeroed (above) before the event the sweep's mean kernels wait behind
     if (ev_select) NNGP_HIP_CHECK(hipEventRecord(ev_select, st));   // the lists are ready
-    a.m = m; a.d = d; a.n_fits = (int)nfp;
-    a.D2 = D2; a.Y = ymT; a.ys_c = m; a.ys_r = 1;
-    a.theta0 = theta0; a.fatol = F.fatol; a.xatol = F.xatol; a.maxfev = F.maxfev; a.R = F.n_restarts;
-    a.fits_out = fits_out;
-    a.qs_D2 = (int64_t)m * m; a.qs_Y = (int64_t)d * m; a.qs_th = (int64_t)nfp * 2; a.qs_fits = (int64_t)nfp * 4;
-    a.jmajor = env_int("NNGP_NM_JMAJOR", 1);   // (run_nm_parked; Burgers 0.328 -> 0.317 s)
+    batch_fit_args(a, F, d, D2, ymT, theta0, fits_out);
     a.done = done;
     const NMArgs p = a;   // (run_nm adjusts its copy's launch fields)
     // latency: a wave per fit (the re-speculation window the sweep waits on); else packed fits.
@@ -2144,6 +2166,167 @@ int chain_miss_fits(const TrainSet &T, const FitSet &F, const double *theta0, co
     return fits_then_mean(a, st);
 }
 
+// ---- predictions on prescribed neighbour lists (nngp_predict_listed, nngp_listed_sweep) -------
+// A list replaces the kNN: no distance launch, no select.  What the select handed on is rebuilt from
+// the list -- y_m^T by listed_gather_kernel, D2 (and kd2) by the pair / wave kernels the select's
+// callers already use for the shapes it does not stage (bitwise pw_sqdiff, as every form is) -- and
+// the fits and means are the batch's.
+
+// ymT[q][c][r] = Y[lists[q][r]][c], the select's layout; queries grid-strided, rows read contiguously
+__global__ void __launch_bounds__(256) listed_gather_kernel(const double *__restrict__ Y, int d, int m, int nq,
+                                                            const int32_t *__restrict__ lists,
+                                                            double *__restrict__ ymT) {
+    const int64_t per = (int64_t)d * m;
+    for (int q = blockIdx.x; q < nq; q += gridDim.x) {
+        const int32_t *li = lists + (size_t)q * m;
+        double *o = ymT + (size_t)q * per;
+        for (int64_t e = threadIdx.x; e < per; e += 256) {
+            const int r = (int)(e / d), c = (int)(e % d);
+            o[(int64_t)c * m + r] = Y[(int64_t)li[r] * d + c];
+        }
+    }
+}
+
+// (the argument checks, the walk over lists_host and the workspace layouts: nngp_listed_host.h)
+static int listed_workspace(const TrainSet &T, const FitSet &F, int nq, ListedWs *w) {
+    int err = 0;
+    char *ws = (char *)workspace(listed_ws_carve(nullptr, nq, T.d, F.m, F.n_fits(T.d)).bytes, &err, WS_PREDICT_BATCH);
+    if (err) return err;
+    *w = listed_ws_carve(ws, nq, T.d, F.m, F.n_fits(T.d));
+    return NNGP_OK;
+}
+
+// The launches of nq listed predictions up to and including their fits: the gather, D2 (with Q also
+// kd2[nq][m] into w.kd2) and all nq*n_fits fits as one packed launch.  lists: DEVICE [nq][m], checked.
+// *p: the batch's fit arguments (for the mean / the prepare launch that follows).
+static int listed_fits(const TrainSet &T, const FitSet &F, const ListedWs &w, const int32_t *lists, const double *Q,
+                       int nq, const double *theta0, double *fits_out, hipStream_t st, NMArgs *p) {
+    const int d = T.d, m = F.m;
+    NMArgs a{};
+    int rc = fill_jitters(a, F.n_jitter, F.jitter_exp_host);
+    if (rc) return rc;
+    hipLaunchKernelGGL(listed_gather_kernel, dim3((unsigned)std::min(nq, 1024)), dim3(256), 0, st, T.Y, d, m, nq,
+                       lists, w.ymT);
+    NNGP_LAUNCH_CHECK();
+    double *kd2 = Q ? w.kd2 : nullptr;
+    const int d2_tasks = m * (m + 1) / 2 + (kd2 ? m : 0);
+    if (d2_by_waves(m, d))
+        hipLaunchKernelGGL(d2_wave_kernel, dim3((unsigned)d2_tasks, (unsigned)nq), dim3(64), 0, st, T.X, lists, m, d,
+                           Q, w.D2, kd2);
+    else
+        hipLaunchKernelGGL(d2_pairs_kernel, dim3((unsigned)((d2_tasks + 255) / 256), (unsigned)nq), dim3(256), 0, st,
+                           T.X, lists, m, d, Q, w.D2, kd2);
+    NNGP_LAUNCH_CHECK();
+    batch_fit_args(a, F, d, w.D2, w.ymT, theta0, fits_out ? fits_out : w.fits);
+    *p = a;   // (run_nm adjusts its copy's launch fields)
+    return run_nm(a, false, st, nq, WS_PREDICT_BATCH_QUEUE);
+}
+
+// the arguments both sweep forms share: slice j = i - I reads U1[i], lists[j], AP[j]
+struct ListedArgs {
+    const double *t;           // [N+1]
+    int I, nq, d, m, maxm;     // maxm: the padded fit size AP was prepared at
+    const double *X;           // [rows][d]
+    const int32_t *lists;      // [nq][m]
+    const double *AP;          // [nq][d][HM_STRIDE(maxm)] (gp_pre_kernel)
+    double *U1, *UG1;          // [N+1][d]
+    double *preds;             // [nq][d] or null
+};
+
+// The means of four coordinates c = cbase + cstep*u of one 16-lane group, from their prepared halves
+// and the slice's kd2 -- the HitMean block of knn_select_dev (bitwise gp_mean_dev): all four
+// coordinates' loads issued before the sums; every group runs every trip (the DPP row sums).
+// store(c, mean) runs on the group's lane 0 for c < d.
+template <typename S>
+__device__ __forceinline__ void listed_finish4(const double *__restrict__ AP, int d, int m, int maxm, int l,
+                                               const double (&kd)[4], int cbase, int cstep, S &&store) {
+    constexpr int CH = 4;
+    const int rpl = (maxm + 15) / 16, hs = HM_STRIDE(maxm);
+    const bool big = maxm > 32;
+    double al[CH][4], cq[CH], ps[CH], okv[CH];
+#pragma unroll
+    for (int u = 0; u < CH; u++) {
+        const int c = cbase + cstep * u;
+        const double *ap = AP + (int64_t)(c < d ? c : 0) * hs;
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const int row = l + 16 * s;
+            al[u][s] = (s < rpl && row < maxm) ? ap[row] : 0.0;
+        }
+        cq[u] = ap[maxm];
+        ps[u] = ap[maxm + 1];
+        okv[u] = ap[maxm + 2];
+    }
+#pragma unroll
+    for (int u = 0; u < CH; u++) {
+        const int c = cbase + cstep * u;
+        const double mean = gp_mean_finish<4>(m, l, rpl, big, kd, cq[u], ps[u], al[u], okv[u] != 0.0);
+        if (c < d && l == 0) store(c, mean);
+    }
+}
+
+// The whole listed sweep as ONE wave (systems with an in-kernel G, d <= CHAIN_QMAX): per slice
+//   1. G(U1[i]) by chain_lane_g (lane 0) or chain_burgers_g (the wave), into LDS
+//   2. kd2[r] = pw_sqdiff(X[list[r]], U1[i]) by lane r < m, into LDS
+//   3. the d means by 16-lane groups from AP and kd2; U1[i+1] = mean + UG1[i+1]
+// The state, G's output and kd2 change owner lanes between the phases: they pass through LDS with a
+// barrier on both sides (one wave: the barrier is a wait on its own LDS traffic), and the global
+// rows are written by the lane that owns the value, never re-read here.  No other workgroup, no
+// flag, no host round trip: the kernel is as stream-ordered as any launch.
+__global__ void __launch_bounds__(64) listed_chain_kernel(GArgs g, ListedArgs a) {
+    __shared__ __attribute__((aligned(16))) double su[CHAIN_QMAX], sg[CHAIN_QMAX];   // U1[i], G(U1[i])
+    __shared__ double skd[MAX_M];
+    const int lane = threadIdx.x, l = lane & 15, grp = lane >> 4;
+    const int d = a.d, m = a.m;
+    for (int e = lane; e < d; e += 64) su[e] = a.U1[(size_t)a.I * d + e];
+    __syncthreads();
+    for (int j = 0; j < a.nq; j++) {
+        const int i = a.I + j;
+        double *ug_next = a.UG1 + (size_t)(i + 1) * d, *u_next = a.U1 + (size_t)(i + 1) * d;
+        double *pr = a.preds ? a.preds + (size_t)j * d : nullptr;
+        if (g.gkind == 1) chain_burgers_g(g.fa, g.ept, g.order, g.lin, g.norm, lane, a.t[i], a.t[i + 1], g.g_steps, su, sg);
+        else if (lane == 0) chain_lane_g(g.la, g.sys, g.order, g.lin, g.norm, a.t[i], a.t[i + 1], g.g_steps, su, sg);
+        if (lane < m) skd[lane] = pw_sqdiff(a.X + (int64_t)a.lists[(size_t)j * m + lane] * d, su, d);
+        __syncthreads();   // sg and skd are complete; every read of su is done
+        double kd[4];
+#pragma unroll
+        for (int s = 0; s < 4; s++) kd[s] = skd[l + 16 * s < m ? l + 16 * s : 0];
+        const double *AP = a.AP + (size_t)j * d * HM_STRIDE(a.maxm);
+        for (int c0 = 0; c0 < d; c0 += 16)
+            listed_finish4(AP, d, m, a.maxm, l, kd, c0 + grp, 4, [&](int c, double mean) {
+                const double ug = sg[c], v = mean + ug;
+                if (pr) pr[c] = mean;
+                ug_next[c] = ug;
+                u_next[c] = v;
+                su[c] = v;
+            });
+        __syncthreads();   // su is the next slice's state; skd and sg are free again
+    }
+}
+
+// One slice of the launch form (after its G launch): 64 coordinates per workgroup, four per 16-lane
+// group.  kd2_pre: the slice's kd2 from kd2_wave_kernel (the shapes d2_by_waves takes), else every
+// workgroup's lanes r < m compute pw_sqdiff themselves (d <= 128: m short sums).
+__global__ void __launch_bounds__(256) listed_mean_kernel(ListedArgs a, int j, const double *__restrict__ kd2_pre) {
+    __shared__ double skd[MAX_M];
+    const int tid = threadIdx.x, l = tid & 15, grp = tid >> 4;
+    const int d = a.d, m = a.m, i = a.I + j;
+    const double *q = a.U1 + (size_t)i * d, *ug_next = a.UG1 + (size_t)(i + 1) * d;
+    double *u_next = a.U1 + (size_t)(i + 1) * d;
+    double *pr = a.preds ? a.preds + (size_t)j * d : nullptr;
+    if (tid < m)
+        skd[tid] = kd2_pre ? kd2_pre[tid] : pw_sqdiff(a.X + (int64_t)a.lists[(size_t)j * m + tid] * d, q, d);
+    __syncthreads();
+    double kd[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) kd[s] = skd[l + 16 * s < m ? l + 16 * s : 0];
+    listed_finish4(a.AP + (size_t)j * d * HM_STRIDE(a.maxm), d, m, a.maxm, l, kd, (int)blockIdx.x * 64 + grp, 16,
+                   [&](int c, double mean) {
+                       if (pr) pr[c] = mean;
+                       u_next[c] = mean + ug_next[c];
+                   });
+}
+
 }  // namespace nngp
 
 extern "C" int64_t nngp_chain_stats(int64_t *slices_out) {
@@ -2203,6 +2386,109 @@ extern "C" int nngp_predict_batch(const double *X, const double *Y, int64_t rows
         if (rc) return rc;
     }
     return NNGP_OK;
+}
+
+extern "C" int nngp_predict_listed(const double *X, const double *Y, int64_t rows, int d, const double *Q, int n_q,
+                                   const int32_t *lists_host, int m, int n_jitter, const double *jitter_exp_host,
+                                   int n_restarts, const double *theta0, double fatol, double xatol, int maxfev,
+                                   double *preds_out, const double *bias, double *out, double *fits_out,
+                                   void *stream) {
+    NNGP_REQUIRE(Q != nullptr, "Q is NULL");
+    NNGP_REQUIRE(preds_out != nullptr, "preds_out is NULL");
+    NNGP_REQUIRE((bias == nullptr) == (out == nullptr), "bias and out are given both or neither");
+    NNGP_REQUIRE(n_q >= 0, "n_q must be >= 0 (got %d)", n_q);
+    int rc = listed_check(X, Y, rows, d, lists_host, n_q, m, n_jitter, jitter_exp_host, n_restarts, theta0, maxfev,
+                          MAX_M, MAX_JIT);
+    if (rc) return rc;
+    if (n_q == 0) return NNGP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const TrainSet T{X, Y, rows, d};
+    const FitSet F{m, n_jitter, jitter_exp_host, n_restarts, fatol, xatol, maxfev};
+    const int64_t n_fits = F.n_fits(d), chunk = predict_batch_chunk(n_fits);
+    for (int64_t q0 = 0; q0 < n_q; q0 += chunk) {   // nngp_predict_batch's chunks, the first the largest
+        const int nq = (int)std::min<int64_t>(chunk, n_q - q0);
+        ListedWs w;
+        if ((rc = listed_workspace(T, F, nq, &w)) != NNGP_OK) return rc;
+        NNGP_HIP_CHECK(hipMemcpyAsync(w.lists, lists_host + q0 * m, sizeof(int32_t) * (size_t)nq * m,
+                                      hipMemcpyHostToDevice, st));
+        NMArgs mb;
+        rc = listed_fits(T, F, w, w.lists, Q + q0 * d, nq, theta0 + q0 * n_fits * 2,
+                         fits_out ? fits_out + q0 * n_fits * 4 : nullptr, st, &mb);
+        if (rc) return rc;
+        mb.kd2 = w.kd2; mb.preds = preds_out + q0 * d;
+        mb.bias = bias ? bias + q0 * d : nullptr; mb.out = out ? out + q0 * d : nullptr;
+        if ((rc = run_mean(mb, st, nq)) != NNGP_OK) return rc;
+    }
+    return NNGP_OK;
+}
+
+extern "C" int nngp_listed_sweep(const nngp_system *sys, int g_tableau, int g_step_mode, int64_t g_steps,
+                                 const double *t, int I, int N, double *U1, double *UG1, const double *X,
+                                 const double *Y, int64_t rows, const int32_t *lists_host, int m, int n_jitter,
+                                 const double *jitter_exp_host, int n_restarts, const double *theta0, double fatol,
+                                 double xatol, int maxfev, double *preds_out, float *g_ms_out, void *stream) {
+    NNGP_REQUIRE(sys != nullptr, "sys is NULL");
+    NNGP_REQUIRE(t != nullptr, "t is NULL");
+    NNGP_REQUIRE(U1 != nullptr, "U1 is NULL");
+    NNGP_REQUIRE(UG1 != nullptr, "UG1 is NULL");
+    NNGP_REQUIRE(I >= 0, "I must be >= 0 (got %d)", I);
+    const int d = sys->d;
+    const int64_t n_sl = std::max<int64_t>((int64_t)N - I, 0);
+    int rc = listed_check(X, Y, rows, d, lists_host, n_sl, m, n_jitter, jitter_exp_host, n_restarts, theta0, maxfev,
+                          MAX_M, MAX_JIT);
+    if (rc) return rc;
+    const bool one_wave = g_in_kernel(sys, g_step_mode) && d <= CHAIN_QMAX;
+    GTimer gt;   // (the one-wave form reports no G time: *g_ms_out stays 0)
+    if ((rc = gt.begin(g_ms_out, one_wave ? 0 : n_sl, g_time_stride())) != NNGP_OK) return rc;
+    if (n_sl == 0) return NNGP_OK;
+    const int nq = (int)n_sl;
+    hipStream_t st = (hipStream_t)stream;
+    const Coarse G{sys, g_tableau, g_step_mode, g_steps, t};
+    const TrainSet T{X, Y, rows, d};
+    const FitSet F{m, n_jitter, jitter_exp_host, n_restarts, fatol, xatol, maxfev};
+    const int64_t n_fits = F.n_fits(d);
+    GArgs ga{};
+    if (one_wave && (rc = g_args(G, ga)) != NNGP_OK) return rc;
+    const int maxm = maxm_for(m);
+    int err = 0;
+    char *ws = (char *)workspace(listed_sweep_ws_carve(nullptr, nq, d, m, maxm).bytes, &err, WS_LISTED_SWEEP);
+    if (err) return err;
+    const ListedSweepWs sw = listed_sweep_ws_carve(ws, nq, d, m, maxm);
+    double *AP = sw.AP, *kd2 = sw.kd2;
+    int32_t *pre_done = sw.pre_done, *lists = sw.lists;
+    NNGP_HIP_CHECK(hipMemcpyAsync(lists, lists_host, sizeof(int32_t) * (size_t)nq * m, hipMemcpyHostToDevice, st));
+    NNGP_HIP_CHECK(hipMemsetAsync(pre_done, 0, sizeof(int32_t) * (size_t)nq, st));
+    // every slice's fits and prepared coordinates before the chain: nothing of them depends on a query
+    const int64_t chunk = predict_batch_chunk(n_fits);
+    for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+        const int nqc = (int)std::min<int64_t>(chunk, nq - q0);
+        ListedWs w;
+        if ((rc = listed_workspace(T, F, nqc, &w)) != NNGP_OK) return rc;
+        NMArgs p;
+        if ((rc = listed_fits(T, F, w, lists + q0 * m, nullptr, nqc, theta0 + q0 * n_fits * 2, nullptr, st, &p)) != NNGP_OK)
+            return rc;
+        if ((rc = run_pre(p, AP + (size_t)q0 * d * HM_STRIDE(maxm), pre_done + q0, nqc, st)) != NNGP_OK) return rc;
+    }
+    const ListedArgs a{t, I, nq, d, m, maxm, X, lists, AP, U1, UG1, preds_out};
+    if (one_wave) {
+        hipLaunchKernelGGL(listed_chain_kernel, dim3(1), dim3(64), 0, st, ga, a);
+        NNGP_LAUNCH_CHECK();
+        return NNGP_OK;
+    }
+    const bool kd2_pre = d2_by_waves(m, d);
+    for (int j = 0; j < nq; j++) {
+        const int i = I + j;
+        if ((rc = gt.launch(G, i, (size_t)j, U1 + (size_t)i * d, UG1 + (size_t)(i + 1) * d, st)) != NNGP_OK) return rc;
+        if (kd2_pre) {
+            hipLaunchKernelGGL(kd2_wave_kernel, dim3((unsigned)m), dim3(64), 0, st, X, lists + (size_t)j * m, m, d,
+                               U1 + (size_t)i * d, kd2);
+            NNGP_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(listed_mean_kernel, dim3((unsigned)((d + 63) / 64)), dim3(256), 0, st, a, j,
+                           kd2_pre ? kd2 : (const double *)nullptr);
+        NNGP_LAUNCH_CHECK();
+    }
+    return gt.finish();
 }
 
 extern "C" int nngp_predict_range(const double *X, const double *Y, int64_t rows, int d, const double *new_x,

@@ -138,6 +138,9 @@ class Parareal(_Parareal):
         model = args[0] if args else kwargs.get('model', 'parareal')
         if isinstance(model, str) and model.lower() in ('elm', 'nn'):   # new_lib's driver has no ELM / k-NN branch
             raise Exception('Not implemented')
+        if kwargs.get('nntype') not in (None, 'nn'):   # nor nnGPara_with_time.py's neighbour-set variants
+            raise NotImplementedError('the legacy driver has no nntype variants (they read the modern driver\'s '
+                                      'data_x table): use nngp_amd.Parareal')
         if kwargs.get('comp_mdls') is not None:   # nor Figure_2.py's comparison loop
             raise NotImplementedError('the legacy driver has no model comparison (comp_mdls): use nngp_amd.Parareal')
         self._setup_solver()

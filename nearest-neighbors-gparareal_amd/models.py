@@ -373,6 +373,263 @@ class NNGP_p(ModelAbstr):
         self.pool = pool
 
 
+NNTYPES = ('nn', 'col+rnd', 'col_only', 'row_col', 'row', 'col_full')
+ALTERNATION_TURNS = 101   # the reference's cycler leaves its loop after turn c == 100 (nnGPara_with_time.py:112)
+
+
+def _alternation(i, N):
+    """The intervals i, i+1, i-1, i+2, ... as the reference's my_cycler yields them
+    (nnGPara_with_time.py:98-115): a turn takes the next interval downwards, then the next upwards; a
+    side that has run out is skipped, the loop ends in the turn that finds both run out, and after
+    ALTERNATION_TURNS turns whatever is left."""
+    lo, hi = i, i + 1
+    for _ in range(ALTERNATION_TURNS):
+        lo_out = lo < 0
+        if not lo_out:
+            yield lo
+            lo -= 1
+        if hi < N:
+            yield hi
+            hi += 1
+        elif lo_out:
+            return
+
+
+class NNGP_alt(NNGP_p):
+    """The reference's neighbour-set variants of nnGParareal (NNGP_alt, nnGPara_with_time.py:27-184):
+    the nnGP correction on neighbours chosen by their place in the (interval, iteration) table of
+    starting values instead of by distance.  nntype 'nn' is NNGP_p itself.  For the others the list
+    of slice i at iteration k depends on (i, k), the table's NaN pattern and (col+rnd) the model's
+    second generator only -- never on the query -- so neighbour_lists gives every slice's list
+    before the sweep, and the device runs them as prescribed lists (nngp_listed_sweep /
+    nngp_predict_listed).  Cells are written (interval, iteration):
+      col_only  (i, 0) .. (i, k): m = k + 1, nn is not used
+      col+rnd   c = min(nn, k+1) cells (i, k+1-c) .. (i, k), then of the first nn entries of
+                rng2.permutation(rows) (one draw per slice, in slice order) those that are not the
+                first training row sharing a coordinate value with one of the column rows, nn - c of them
+      row_col   every filled cell by |k' - k| + |i' - i|, ties interval-major (the reference's tie order
+                is numpy's unstable argsort's: DESIGN.md 3.3c)
+      row       iterations k, k-1, .., 0; in each the intervals i, i+1, i-1, i+2, ..
+      col_full  intervals i, i+1, i-1, ..; in each the iterations k, .., 0
+    with empty (NaN) cells skipped, at most 101 alternation turns, and the first nn taken.  nn follows
+    n_neighbours() (the reference reads self.nn directly for the last three, so 'adaptive' fails there)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        nntype = kwargs.get('nntype')
+        if nntype not in NNTYPES:
+            raise ValueError(f'nntype={nntype!r}: expected one of {NNTYPES}')
+        self.nntype = nntype
+        self.name = 'NNGP' + str(nntype)
+        self.rng2 = np.random.default_rng(self.seed)
+        self.data_x = None
+        self._cells = None
+
+    @property
+    def listed(self):
+        """The neighbours are prescribed lists (every nntype but 'nn')."""
+        return self.nntype != 'nn'
+
+    def fit(self, x, y, k, *args, **kwargs):
+        """The parent's fit, plus the table data_x [N][n][>= k+1] (kept, not copied: NaN where an
+        interval had converged) and the cell -> training-row map.  The driver appends the filled
+        intervals of column k' as one block per iteration, so
+            row(i, k') = off[k'] + i - first[k'],   first[k'] = the first filled interval of column k'."""
+        super().fit(x, y, k, *args, **kwargs)
+        if not self.listed:
+            return
+        data_x = kwargs.get('data_x')
+        if data_x is None:
+            raise NotImplementedError(f"nntype='{self.nntype}' selects neighbours from the table of starting "
+                                      "values: fit needs data_x (PararealLight and the lag_k training sets keep none)")
+        filled = ~np.isnan(data_x[:, :, :k + 1]).any(axis=1)   # [N][k+1]
+        N = filled.shape[0]
+        count = filled.sum(axis=0)
+        first = np.where(count > 0, filled.argmax(axis=0), N)
+        if not all(filled[first[c]:, c].all() for c in range(k + 1)):
+            raise ValueError('data_x: the filled intervals of a column must be one block up to the last interval')
+        off = np.concatenate([[0], np.cumsum(count)])
+        if off[-1] != int(np.shape(x)[0]):
+            raise ValueError(f'data_x holds {off[-1]} filled cells up to iteration {k} but the training set has '
+                             f'{int(np.shape(x)[0])} rows')
+        self.data_x = data_x
+        self._cells = (filled, first, off[:-1])
+
+    def cell_row(self, i, kk):
+        """The training row of cell (interval i, iteration kk)."""
+        filled, first, off = self._cells
+        if not filled[i, kk]:
+            raise ValueError(f'cell (interval {i}, iteration {kk}) is empty')
+        return int(off[kk] + i - first[kk])
+
+    def _host_x(self):
+        """The training inputs on the host, from the table (no device copy): block k' = column k'."""
+        filled, first, _ = self._cells
+        return np.concatenate([self.data_x[first[c]:, :, c] for c in range(filled.shape[1])])
+
+    def list_size(self):
+        """m of this iteration's lists."""
+        if self.nntype == 'col_only':
+            m = self.k + 1
+            if m > MAX_NEIGHBOURS:
+                raise ValueError(f"nntype='col_only' asks for m={m} neighbours at iteration {self.k}; the GPU nnGP "
+                                 f'correction supports up to {MAX_NEIGHBOURS}')
+            return m
+        return self.n_neighbours()
+
+    def _cells_of(self, i, nn):
+        """The first nn filled cells (interval, iteration) of slice i in the order of self.nntype."""
+        filled, k = self._cells[0], self.k
+        N = filled.shape[0]
+        if self.nntype == 'row_col':
+            dist = np.abs(np.arange(k + 1)[None, :] - k) + np.abs(np.arange(N)[:, None] - i)
+            flat = np.argsort(dist, axis=None, kind='stable')
+            flat = flat[filled.reshape(-1)[flat]][:nn]
+            return [(int(f // (k + 1)), int(f % (k + 1))) for f in flat]
+        if self.nntype == 'row':
+            order = ((c, kk) for kk in range(k, -1, -1) for c in _alternation(i, N))
+        else:   # col_full
+            order = ((c, kk) for c in _alternation(i, N) for kk in range(k, -1, -1))
+        cells = []
+        for c, kk in order:
+            if filled[c, kk]:
+                cells.append((c, kk))
+                if len(cells) == nn:
+                    break
+        return cells
+
+    def neighbour_lists(self, I, N):
+        """int32 [N-I][m]: the ordered training rows of slices i = I .. N-1 at the fitted iteration
+        (consumes one rng2 permutation per slice for col+rnd).  ValueError where a slice has fewer than
+        m candidates (the reference dies there on an exhausted generator)."""
+        if not self.listed:
+            raise ValueError("nntype='nn' has no prescribed lists: its neighbours depend on the query")
+        if self._cells is None:
+            raise AttributeError("'NNGP_alt' has no table yet: call fit(x, y, k, data_x=...) first")
+        k, m = self.k, self.list_size()
+        rows = int(self._cells[2][-1] + self._cells[0][:, -1].sum())
+        out = np.empty((max(N - I, 0), m), dtype=np.int32)
+        x = self._host_x() if self.nntype == 'col+rnd' else None
+        for i in range(I, N):
+            if self.nntype == 'col_only':
+                lst = [self.cell_row(i, kk) for kk in range(k + 1)]
+            elif self.nntype == 'col+rnd':
+                c = min(m, k + 1)
+                lst = [self.cell_row(i, kk) for kk in range(k + 1 - c, k + 1)]
+                # the first training row with ANY coordinate equal to the column row (np.any(x == row,
+                # axis=1).argmax(), nnGPara_with_time.py:62) -- not necessarily the row itself
+                removed = {int(np.argmax(np.any(x == x[r][None, :], axis=1))) for r in lst}
+                cands = self.rng2.permutation(rows)[:m]
+                lst += [int(r) for r in cands if int(r) not in removed][:m - c]
+            else:
+                lst = [self.cell_row(c, kk) for c, kk in self._cells_of(i, m)]
+            if len(lst) < m:
+                raise ValueError(f"nntype='{self.nntype}' at iteration {k}, interval {i}: {len(lst)} neighbours "
+                                 f'are available, {m} are needed')
+            out[i - I] = lst
+        return out
+
+    # ---------------------------------------------------------------------------- device path
+    def predict_listed_device(self, Q, lists, theta0=None, out=None, bias=None, preds=None, fits_out=None,
+                              stream=None):
+        """Corrections at every row of Q [nq][n] on the prescribed lists [nq][m] (host int32), one launch
+        set (nngp_predict_listed).  Arguments as predict_batch_device."""
+        import torch
+        X, Y = self.device_xy()
+        rows, n = int(X.shape[0]), self.n
+        _knn_tensor(X, 'x', (rows, n), X.device)
+        _knn_tensor(Y, 'y', (rows, n), X.device)
+        if not torch.is_tensor(Q) or Q.dim() != 2:
+            raise ValueError('Q must be a device tensor of shape [n_q][n]')
+        nq, nf = int(Q.shape[0]), self.n_fits
+        lists = np.ascontiguousarray(lists, dtype=np.int32)
+        if lists.ndim != 2 or lists.shape[0] != nq:
+            raise ValueError(f'lists must be [{nq}][m] (got {lists.shape})')
+        m = int(lists.shape[1])
+        q_ptr = _knn_tensor(Q, 'Q', (nq, n), X.device)
+        if (out is None) != (bias is None):
+            raise ValueError('out and bias go together')
+        if theta0 is None:
+            theta0 = torch.tensor(self.draw_thetas(nq), dtype=torch.float64, device=X.device)
+        flat = torch.is_tensor(theta0) and tuple(theta0.shape) == (nq * nf, 2)
+        th_ptr = _knn_tensor(theta0, 'theta0', (nq * nf, 2) if flat else (nq, nf, 2), X.device)
+        if preds is None:
+            preds = torch.empty((nq, n), dtype=torch.float64, device=X.device)
+        if nq == 0:
+            return preds
+        ptr = lambda t, name, shape: None if t is None else _knn_tensor(t, name, shape, X.device)
+        jit, jp = _lib.host_doubles(JITTERS)
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().nngp_predict_listed(
+            X.data_ptr(), Y.data_ptr(), rows, n, q_ptr, nq, lists.ctypes.data, m, len(jit), jp, self.n_restarts,
+            th_ptr, float(self.fatol), float(self.xatol), self.maxfev, ptr(preds, 'preds', (nq, n)),
+            ptr(bias, 'bias', (nq, n)), ptr(out, 'out', (nq, n)), ptr(fits_out, 'fits_out', (nq, nf, 4)), st))
+        self.train_count += nq * nf
+        return preds
+
+    def predict_device(self, X, Y, rows, new_x, theta0, out=None, bias=None, preds=None, fits_out=None, stream=None,
+                       i=None):
+        """One correction on device tensors; for a listed nntype the neighbours are interval i's
+        (one nngp_predict_listed query on the model's training set, which is the driver's X / Y)."""
+        if not self.listed:
+            return super().predict_device(X, Y, rows, new_x, theta0, out=out, bias=bias, preds=preds,
+                                          fits_out=fits_out, stream=stream)
+        if i is None:
+            raise ValueError(f"nntype='{self.nntype}' predicts for an interval: pass i")
+        one = lambda t: None if t is None else t.reshape(1, -1)
+        if preds is None:
+            import torch
+            preds = torch.empty(self.n, dtype=torch.float64, device=new_x.device)
+        self.predict_listed_device(one(new_x), self.neighbour_lists(i, i + 1), theta0=theta0.reshape(1, -1, 2),
+                                   out=one(out), bias=one(bias), preds=one(preds),
+                                   fits_out=None if fits_out is None else fits_out.reshape(1, -1, 4), stream=stream)
+        return preds
+
+    def predict_batch_device(self, Q, theta0=None, out=None, bias=None, preds=None, idx_out=None, fits_out=None,
+                             stream=None, intervals=None):
+        """predict_batch_device; for a listed nntype Q[j] is the starting value of interval intervals[j]
+        (consecutive: the driver's slices) and idx_out receives no list (they are neighbour_lists')."""
+        if not self.listed:
+            return super().predict_batch_device(Q, theta0=theta0, out=out, bias=bias, preds=preds, idx_out=idx_out,
+                                                fits_out=fits_out, stream=stream)
+        if intervals is None or idx_out is not None:
+            raise ValueError(f"nntype='{self.nntype}': pass the queries' intervals=(I, N) and no idx_out")
+        I, N = intervals
+        return self.predict_listed_device(Q, self.neighbour_lists(I, N), theta0=theta0, out=out, bias=bias,
+                                          preds=preds, fits_out=fits_out, stream=stream)
+
+    def predict(self, new_x, prev_F=None, prev_G=None, *args, **kwargs):
+        """The reference's predict (host arrays in / out); a listed nntype needs the interval, i=."""
+        if not self.listed:
+            return super().predict(new_x, prev_F, prev_G, *args, **kwargs)
+        torch = _lib.require_gpu()
+        if kwargs.get('i') is None:
+            raise ValueError(f"nntype='{self.nntype}' predicts for an interval: pass i=")
+        X, Y = self.device_xy()
+        q = torch.tensor(np.asarray(new_x, dtype=np.float64).reshape(-1), device='cuda')
+        th0 = torch.tensor(self.draw_thetas(1), device='cuda')
+        return self.predict_device(X, Y, X.shape[0], q, th0, i=int(kwargs['i'])).cpu().numpy()
+
+    def store(self):
+        table, self.data_x = self.data_x, None   # the driver's own array: the result dict has it already
+        try:
+            new = super().store()
+        finally:
+            self.data_x = table
+        return new
+
+    def state_dict(self):
+        st = super().state_dict()
+        st['settings']['nntype'] = self.nntype
+        st['rng2'] = self.rng2.bit_generator.state
+        return st
+
+    def load_state(self, st):
+        super().load_state(st)
+        if 'rng2' in st:
+            self.rng2.bit_generator.state = st['rng2']
+
+
 def _select_fit(theta, fval, jitter):
     """The per-coordinate choice of models.py:388-395 / 361-365: keep fits with
     fval < 0.9 * min(fval) (all if none), then the first minimum in order (Python min, '<')."""

@@ -27,7 +27,8 @@ import warnings
 import numpy as np
 
 from . import _lib
-from .models import ELM, JITTERS, KNN_MAX_COUNTS, MAX_NEIGHBOURS, NN, BareParareal, GPjax_p, ModelAbstr, NNGP_p
+from .models import (ELM, JITTERS, KNN_MAX_COUNTS, MAX_NEIGHBOURS, NN, BareParareal, GPjax_p, ModelAbstr, NNGP_alt,
+                     NNGP_p)
 from .solver import SolverAbstr
 from .systems import ODE
 
@@ -245,7 +246,11 @@ class Parareal():
         if model.lower() == 'parareal':
             mdl = BareParareal(N=self.N, **kwargs)
         elif model.lower() == 'nngp':
-            mdl = NNGP_p(n=self.n, N=self.N, worker_pool=kwargs['pool'], **kwargs)
+            if kwargs.get('nntype') is not None:   # nnGPara_with_time.py:196-199
+                mdl = NNGP_alt(n=self.n, N=self.N, worker_pool=kwargs['pool'], **kwargs)
+                self._check_listed(mdl, kwargs)
+            else:
+                mdl = NNGP_p(n=self.n, N=self.N, worker_pool=kwargs['pool'], **kwargs)
             # nn='adaptive' grows m = k+2 (models.py:172-175); the GPU fits stop at m = 64, i.e. a
             # run still unconverged after 63 iterations raises there.  Say so before any work.
             es = kwargs.get('early_stop')
@@ -285,6 +290,22 @@ class Parareal():
         self.runs[cstm_mdl_name] = out
         return out
 
+    def _check_listed(self, mdl, kwargs):
+        """What a listed nntype (every one but 'nn') cannot run with, said before any work."""
+        if not mdl.listed:
+            return
+        t = mdl.nntype
+        if self._world() > 1:
+            raise NotImplementedError(f"nntype='{t}' runs on one rank: after the batched fits its sweep is one "
+                                      'short kernel with nothing to shard; supported: a process group of one rank, '
+                                      'or none')
+        if self._light:
+            raise NotImplementedError(f"nntype='{t}' selects neighbours from the table of starting values "
+                                      '(data_x), which PararealLight does not keep: use Parareal')
+        if kwargs.get('lag_k') is not None:
+            raise NotImplementedError(f"nntype='{t}' with lag_k: the lagged training set is a re-ordered subset, "
+                                      'for which the table gives no row numbers')
+
     # ------------------------------------------------------------------------ checkpoints
     def store(self, name, path='', mdl=None, objs=None):
         """Checkpoint (parareal.py:114-139).  The reference pickles the whole Parareal object;
@@ -323,6 +344,9 @@ class Parareal():
         mst = state['model']
         if mst['name'] == 'NNGP':
             mdl = NNGP_p(n=self.n, N=self.N, worker_pool=GpuPool(), **mst['settings'])
+        elif mst['name'].startswith('NNGP') and mst['settings'].get('nntype') is not None:
+            mdl = NNGP_alt(n=self.n, N=self.N, worker_pool=GpuPool(), **mst['settings'])
+            self._check_listed(mdl, kwargs)
         elif mst['name'] == 'GP':
             mdl = GPjax_p(n=self.n, N=self.N, worker_pool=GpuPool(), **mst['settings'])
         elif mst['name'] == 'ELM':   # its constructor arguments; the training set is the dump's x / D
@@ -474,6 +498,24 @@ class Parareal():
         # every sweep entry's leading arguments: the coarse propagator, its grid, the slices, U and U_G
         head = (ctypes.byref(cs), _lib.TABLEAU[solver.G], solver.step_mode, solver.Ng, t_dev.data_ptr(), I, N,
                 U1.data_ptr(), UG1.data_ptr())
+        if isinstance(model, NNGP_alt) and model.listed:
+            # every slice's list is known before the sweep (it never depends on the query): ONE native
+            # call that fits and prepares all slices at once and then runs the short sequential part
+            lists = model.neighbour_lists(I, N)
+            # pinned staging, as for the thetas: the library's upload is then asynchronous (the previous
+            # iteration's finished before that iteration's host copy returned)
+            pin = getattr(self, '_lists_pin', None)
+            if pin is None or pin.numel() < lists.size:
+                pin = self._lists_pin = torch.empty(2 * lists.size, dtype=torch.int32, pin_memory=True)
+            pin[:lists.size].copy_(torch.from_numpy(lists).view(-1))
+            jit, jp = _lib.host_doubles(JITTERS)
+            _lib.check(lib.nngp_listed_sweep(
+                *head, X.data_ptr(), Y.data_ptr(), int(rows), pin.data_ptr(), int(lists.shape[1]), len(jit), jp,
+                model.n_restarts, th0.data_ptr(), float(model.fatol), float(model.xatol), model.maxfev, None,
+                ctypes.byref(g_ms), stream))
+            model.train_count += model.n_fits * (N - I)
+            self.spec_hits.append(0)
+            return g_ms.value / 1e3
         if isinstance(model, NNGP_p) and self._shard_corrections(model):
             return self._correction_sweep_sharded(torch, model, t_dev, I, N, U1, UG1, X, Y, rows, th0, stream)
         if isinstance(model, NNGP_p):
@@ -615,7 +657,8 @@ class Parareal():
             ev.stop(eg, 'G')
             if isinstance(model, NNGP_p):
                 model.predict_device(X, Y, rows, U1[i], th0[j * nf:(j + 1) * nf], out=U1[i + 1],
-                                     bias=UG1[i + 1], preds=P[j], stream=stream)
+                                     bias=UG1[i + 1], preds=P[j], stream=stream,
+                                     **({'i': i} if isinstance(model, NNGP_alt) else {}))
             elif isinstance(model, (ELM, NN)):
                 model.predict_device(U1[i], out=U1[i + 1], bias=UG1[i + 1], preds=P[j], stream=stream)
             else:
@@ -659,7 +702,8 @@ class Parareal():
                 P = torch.empty((nq, n), dtype=torch.float64, device=U1.device)
                 if isinstance(m, NNGP_p):
                     th0 = torch.tensor(m.draw_thetas(nq), dtype=torch.float64, device=U1.device)
-                    m.predict_batch_device(Q, theta0=th0, preds=P, stream=stream)
+                    m.predict_batch_device(Q, theta0=th0, preds=P, stream=stream,
+                                           **({'intervals': (I, N)} if isinstance(m, NNGP_alt) else {}))
                 elif isinstance(m, GPjax_p):
                     for j in range(nq):
                         m.predict_device(Q[j], out=P[j], stream=stream)
@@ -688,7 +732,8 @@ class Parareal():
             if isinstance(model, NNGP_p):
                 j = i - I
                 model.predict_device(X, Y, rows, U1[i], th0[j * nf:(j + 1) * nf], out=U1[i + 1],
-                                     bias=UG1[i + 1], stream=stream)
+                                     bias=UG1[i + 1], stream=stream,
+                                     **({'i': i} if isinstance(model, NNGP_alt) else {}))
             elif isinstance(model, (GPjax_p, ELM, NN)):
                 model.predict_device(U1[i], out=U1[i + 1], bias=UG1[i + 1], stream=stream)
             else:   # (uF - uG_prev) + uG_new   (models.py:82-83, parareal.py:382)
